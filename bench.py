@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native dense backend for faer.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gemm|llt|lu|qr|gemv|fplu|cpqr|tridiag|bidiag|hess] [--no-extras] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gemm|llt|lu|qr|gemv|fplu|cpqr|tridiag|bidiag|hess]
+                  [--dump-outputs DIR] [--full [--no-extras] [--no-cpu]]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps and prints ONE JSON line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, ...).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all:
+larger outputs as a fixed, seeded sample; `dump_outputs`); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.  Everything else the benchmark measures -- `roofline`, `others`,
+`cpu_baseline`, the extras of a distributed run -- runs only with --full (--no-extras / --no-cpu leave parts of it out).
 
 Metric (BASELINE.json): achieved fp64 GFLOP/s.  A "step" is one pass of the hot path over one batch of
 synthetic input that is already resident in HBM when the timed region starts:
@@ -16,14 +24,14 @@ synthetic input that is already resident in HBM when the timed region starts:
 With --gpus N > 1 (launched by torch.distributed.run, one rank per GPU) and no --workload the headline is
 BASELINE.json configs[3]: the partial-pivot LU of a 16384^2 matrix, 1-D block-cyclic columns over the N ranks, one
 RCCL broadcast per factored panel through the library's own transport (`resolve_run` below) => strong scaling;
-`value` is the whole-job rate, `per_rank.ncclCommCount` must equal N, `lu_1gpu_same_run` is the single-GPU LU of
-the same size timed on rank 0 in the same run (the N = 1 point of the curve; it is also `others.lu_f64_n16384` of
-the --gpus 1 line).  `others` then carries the collective-free weak-scaling GEMM (every rank multiplies the same
+`value` is the whole-job rate, `per_rank.ncclCommCount` must equal N; with --full, `lu_1gpu_same_run` is the single-GPU
+LU of the same size timed on rank 0 in the same run (the N = 1 point of the curve; it is also `others.lu_f64_n16384` of
+the --gpus 1 line), and `others` carries the collective-free weak-scaling GEMM (every rank multiplies the same
 A by its own N x 8192 slice of B) and the block-cyclic LU at N = 65536.  Rank 0 prints ONE JSON line.
 BENCH_FORCE_DIST=1 with --gpus 1 runs exactly that code path with ONE rank (process group, RCCL communicator, block-cyclic
 driver, the N = 65536 entry): a dry run of the multi-GPU default on a one-GPU box (profiles/r05_bench_dryrun_dist_one_rank.json).
 
-The line also carries
+With --full the line also carries
   "roofline":     the dominant kernel (the MFMA GEMM) against the fp64 MFMA peak, timed with HIP events on the
                   stream the kernel runs on;
   "cpu_baseline": the CPU oracle (a port of faer's algorithm, see oracle/) timed on a bounded sample on this
@@ -112,6 +120,49 @@ FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X fp64 matrix peak (AMD datasheet; BASELIN
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md chip table
 HBM_PEAK_GBS = 8000.0
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all arrays of one run together
+DUMP_WHOLE_BYTES = 16 << 20   # an output up to this size is written whole ...
+DUMP_SAMPLE = 1 << 20         # ... a larger one as this many entries at fixed, seeded positions
+DUMP_SEED = 2024
+
+
+def dump_outputs(dirname, outputs, suffix=""):
+    """--dump-outputs: writes what the caller of the last timed step received, {name: (array, lower)} of make_workload, as
+    DIR/<name><suffix>.npy in float32 / float64 (permutations as float64, exact).  An output of at most DUMP_WHOLE_BYTES is written
+    whole (its lower triangle when `lower`); a larger one as DUMP_SAMPLE entries, 1-D, at positions drawn from DUMP_SEED and sorted
+    in column-major order (mirrored into the lower triangle when `lower`): the same positions in every run with the same arguments,
+    so two builds can be compared entry for entry.  Returns {file name: shape}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    left, written = DUMP_BUDGET_BYTES, {}
+    for name, (x, lower) in outputs.items():
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.asarray(x, dtype=np.float64))
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float64)
+        if x.numel() * x.element_size() <= min(DUMP_WHOLE_BYTES, left):
+            arr = x.cpu().numpy()
+            if lower:
+                arr = np.tril(arr)
+        else:
+            x2 = x if x.dim() == 2 else x.reshape(-1, 1)
+            m, n = x2.shape
+            rng = np.random.default_rng(DUMP_SEED)
+            k = min(DUMP_SAMPLE, m * n, left // x.element_size())
+            i, j = rng.integers(0, m, k), rng.integers(0, n, k)
+            if lower:
+                i, j = np.maximum(i, j), np.minimum(i, j)
+            order = np.argsort(j * m + i, kind="stable")
+            ii, jj = (torch.from_numpy(v[order]).to(x.device) for v in (i, j))
+            arr = x2[ii, jj].cpu().numpy()
+        fname = f"{name}{suffix}.npy"
+        np.save(os.path.join(dirname, fname), np.ascontiguousarray(arr))
+        left -= arr.nbytes
+        written[fname] = list(arr.shape)
+    return written
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -127,7 +178,14 @@ def main():
     ap.add_argument("--transport", default=None, choices=["torch", "rccl"],
                     help="multi-GPU lu/llt: broadcast through torch.distributed (RCCL under the nccl backend) or the library's own "
                          "RCCL transport (ncclBroadcast on a dedicated stream, no Python callback in the loop)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and kernel-class profile, `others`, the CPU baselines, "
+                         "the distributed run's extras (off: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     args.workload, args.transport, defaulted = resolve_run(args.gpus, args.workload, args.transport)
 
     import numpy as np
@@ -197,7 +255,9 @@ def main():
 
     # ------------------------------------------------------------------ workloads
     def make_workload(name, n_override=0):
-        """returns (step_fn, flops_per_step, overhead_fn, label, dtype_name)"""
+        """returns (step_fn, flops_per_step, overhead_fn, label, dtype_name, outputs_fn); outputs_fn() -> {name: (array, lower)}, what
+        the caller of the last step received (`lower`: only the lower triangle is the result)"""
+        last = {}  # host-side results of the last step (permutations)
         if name in ("gemm", "gemm4096", "sgemm"):
             # "gemm4096": the mid-size product the factorizations live on; "sgemm": north_star's fp32 MFMA GEMM
             n = n_override or (4096 if name == "gemm4096" else 8192)
@@ -209,7 +269,8 @@ def main():
             def step():
                 F.matmul(c, F.ACCUM_REPLACE, a, b, 1.0)
 
-            return step, 2.0 * n ** 3, None, (f"sgemm_f32_n{n}" if name == "sgemm" else f"dgemm_f64_n{n}"), ("f32" if name == "sgemm" else "f64")
+            return step, 2.0 * n ** 3, None, (f"sgemm_f32_n{n}" if name == "sgemm" else f"dgemm_f64_n{n}"), ("f32" if name == "sgemm" else "f64"), \
+                lambda: {"c": (c, False)}
         if name == "gemv":
             # level-2 shape of the same entry point (matmul with one rhs column): an HBM stream, not an MFMA kernel
             n = n_override or 16384
@@ -220,7 +281,7 @@ def main():
             def step():
                 F.matmul(yv, F.ACCUM_REPLACE, a, xv, 1.0)
 
-            return step, 2.0 * n * n, None, f"dgemv_f64_n{n}", "f64"
+            return step, 2.0 * n * n, None, f"dgemv_f64_n{n}", "f64", lambda: {"y": (yv, False)}
         if name == "llt" and dist is not None:
             # 1-D block-cyclic columns over the ranks, one RCCL broadcast per factored column panel, look-ahead
             # (csrc/dist_llt.h); the total work is fixed => strong scaling.  The SPD matrix is built per rank from
@@ -245,7 +306,7 @@ def main():
                     F.dist_llt(work, n, nb, rank, world, lambda t, root: dist.broadcast(t, src=root), panel_ws=ws,
                                ibcast=lambda t, root: dist.broadcast(t, src=root, async_op=True))
 
-            return step, n ** 3 / 3.0 / world, lambda: work.copy_(a), f"llt_f64_n{n}_blockcyclic{nb}", "f64"
+            return step, n ** 3 / 3.0 / world, lambda: work.copy_(a), f"llt_f64_n{n}_blockcyclic{nb}", "f64", lambda: {"l_local": (work, False)}
         if name == "llt":
             n = n_override or 16384
             a = colmajor(n, n, torch.float64, 3)
@@ -257,7 +318,7 @@ def main():
                 work.copy_(spd)
                 F.llt_factor_in_place(work)
 
-            return step, n ** 3 / 3.0, lambda: work.copy_(spd), f"llt_f64_n{n}", "f64"
+            return step, n ** 3 / 3.0, lambda: work.copy_(spd), f"llt_f64_n{n}", "f64", lambda: {"l": (work, True)}
         if name == "lu":
             n = n_override or 16384
             if dist is not None:
@@ -273,20 +334,21 @@ def main():
                 def step():
                     work.copy_(a)
                     if rccl is not None:
-                        F.dist_partial_piv_lu(work, n, nb, rank, world, panel_ws=ws, transport=rccl)
+                        last["perm"] = F.dist_partial_piv_lu(work, n, nb, rank, world, panel_ws=ws, transport=rccl)[0]
                     else:
-                        F.dist_partial_piv_lu(work, n, nb, rank, world, lambda t, root: dist.broadcast(t, src=root), panel_ws=ws,
-                                              ibcast=lambda t, root: dist.broadcast(t, src=root, async_op=True))
+                        last["perm"] = F.dist_partial_piv_lu(work, n, nb, rank, world, lambda t, root: dist.broadcast(t, src=root), panel_ws=ws,
+                                                             ibcast=lambda t, root: dist.broadcast(t, src=root, async_op=True))[0]
 
-                return step, 2.0 * n ** 3 / 3.0 / world, lambda: work.copy_(a), f"lu_f64_n{n}_blockcyclic{nb}", "f64"
+                return step, 2.0 * n ** 3 / 3.0 / world, lambda: work.copy_(a), f"lu_f64_n{n}_blockcyclic{nb}", "f64", \
+                    lambda: {"lu_local": (work, False), "row_perm": (last["perm"], False)}
             a = colmajor(n, n, torch.float64, 4)
             work = a.clone()
 
             def step():
                 work.copy_(a)
-                F.partial_piv_lu_factor_in_place(work)
+                last["perm"] = F.partial_piv_lu_factor_in_place(work)[0]
 
-            return step, 2.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"lu_f64_n{n}", "f64"
+            return step, 2.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"lu_f64_n{n}", "f64", lambda: {"lu": (work, False), "row_perm": (last["perm"], False)}
         if name == "qrlit":
             # BASELINE.json configs[4] VERBATIM: 1e6 x 256 fp32.  The reference's own rank test rejects every column from 524288
             # rows on (see "qr" below), so this call does what faer does there -- rank 0, no reflector applied -- and the entry
@@ -301,7 +363,7 @@ def main():
                 work.copy_(a)
                 F.qr_factor_in_place(work, h)
 
-            return step, 2.0 * m * n * n - 2.0 / 3.0 * n ** 3, lambda: work.copy_(a), f"qr_f32_{m}x{n}", "f32"
+            return step, 2.0 * m * n * n - 2.0 / 3.0 * n ** 3, lambda: work.copy_(a), f"qr_f32_{m}x{n}", "f32", lambda: {"qr": (work, False), "q_coeff": (h, False)}
         if name in ("qr", "qrmax"):
             # BASELINE config Q says 1e6 x 256, but faer's own rank test rejects every fp32 column once
             # 16 * eps * nrows >= 1 (nrows >= 524288; qr/no_pivoting/factor.rs:52-58), i.e. the reference does no
@@ -323,7 +385,7 @@ def main():
                 work.copy_(a)
                 F.qr_factor_in_place(work, h)
 
-            return step, 2.0 * m * n * n - 2.0 / 3.0 * n ** 3, lambda: work.copy_(a), f"qr_f32_{m}x{n}", "f32"
+            return step, 2.0 * m * n * n - 2.0 / 3.0 * n ** 3, lambda: work.copy_(a), f"qr_f32_{m}x{n}", "f32", lambda: {"qr": (work, False), "q_coeff": (h, False)}
         if name == "qr64":
             # the same tall-skinny shape in the reference's main arithmetic (fp64): the one-pass path's fp64 instantiation (csrc/tsqr.hip,
             # tsqr_factor64).  faer's Mat layout: column stride padded to 64 bytes
@@ -340,7 +402,7 @@ def main():
                 work.copy_(a)
                 F.qr_factor_in_place(work, h)
 
-            return step, 2.0 * m * n * n - 2.0 / 3.0 * n ** 3, lambda: work.copy_(a), f"qr_f64_{m}x{n}", "f64"
+            return step, 2.0 * m * n * n - 2.0 / 3.0 * n ** 3, lambda: work.copy_(a), f"qr_f64_{m}x{n}", "f64", lambda: {"qr": (work, False), "q_coeff": (h, False)}
         if name == "qrsq":
             # square Householder QR (qr/no_pivoting/factor.rs:137-256 on the classic path of csrc/qr.hip, one-pass panels inside the recursion
             # since the end of round 6): not a BASELINE config, kept in the line because it is the QR every square solve runs
@@ -354,7 +416,7 @@ def main():
                 work.copy_(a)
                 F.qr_factor_in_place(work, h)
 
-            return step, 4.0 / 3.0 * n ** 3, lambda: work.copy_(a), f"qr_f64_n{n}", "f64"
+            return step, 4.0 / 3.0 * n ** 3, lambda: work.copy_(a), f"qr_f64_n{n}", "f64", lambda: {"qr": (work, False), "q_coeff": (h, False)}
         if name == "fplu":
             # LU with full pivoting, a level-2 (HBM bound) algorithm; algorithmic bytes =
             # one read + one write of the trailing matrix per step
@@ -364,9 +426,10 @@ def main():
 
             def step():
                 work.copy_(a)
-                F.full_piv_lu_factor_in_place(work)
+                last["perm"] = F.full_piv_lu_factor_in_place(work)
 
-            return step, 2.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"full_piv_lu_f64_n{n}", "f64"
+            return step, 2.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"full_piv_lu_f64_n{n}", "f64", \
+                lambda: {"lu": (work, False), "row_perm": (last["perm"][0], False), "col_perm": (last["perm"][2], False)}
         if name == "cpqr":
             # QR with column pivoting, HBM bound like the full-pivot LU
             n = n_override or 4096
@@ -377,9 +440,10 @@ def main():
 
             def step():
                 work.copy_(a)
-                F.colpiv_qr_factor_in_place(work, h)
+                last["perm"] = F.colpiv_qr_factor_in_place(work, h)[0]
 
-            return step, 4.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"colpiv_qr_f64_n{n}", "f64"
+            return step, 4.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"colpiv_qr_f64_n{n}", "f64", \
+                lambda: {"qr": (work, False), "q_coeff": (h, False), "col_perm": (last["perm"], False)}
         if name == "tridiag":
             # tridiagonalization (evd/tridiag.rs:274), HBM bound: per column the remaining
             # lower triangle is read and written once (4 n^3 / 3 flop in total)
@@ -393,7 +457,7 @@ def main():
                 work.copy_(a)
                 F.tridiag_in_place(work, h)
 
-            return step, 4.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"tridiag_f64_n{n}", "f64"
+            return step, 4.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"tridiag_f64_n{n}", "f64", lambda: {"a": (work, False), "householder": (h, False)}
         if name == "bidiag":
             # bidiagonalization (svd/bidiag.rs:47), HBM bound: per column the trailing matrix is
             # read + written once and read once more (8 n^3 / 3 flop in total for a square matrix)
@@ -407,7 +471,8 @@ def main():
                 work.copy_(a)
                 F.bidiag_in_place(work, hl, hr)
 
-            return step, 8.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"bidiag_f64_n{n}", "f64"
+            return step, 8.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"bidiag_f64_n{n}", "f64", \
+                lambda: {"a": (work, False), "householder_left": (hl, False), "householder_right": (hr, False)}
         if name == "hess":
             # Hessenberg reduction (evd/hessenberg.rs:549), HBM bound: per column A22 is read +
             # written + read and the rows above are read twice + written (10 n^3 / 3 flop in total)
@@ -420,7 +485,7 @@ def main():
                 work.copy_(a)
                 F.hessenberg_in_place(work, h)
 
-            return step, 10.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"hessenberg_f64_n{n}", "f64"
+            return step, 10.0 * n ** 3 / 3.0, lambda: work.copy_(a), f"hessenberg_f64_n{n}", "f64", lambda: {"a": (work, False), "householder": (h, False)}
         raise ValueError(name)
 
     def timed(fn, steps, warmup):
@@ -483,8 +548,13 @@ def main():
             return r
         return None
 
-    step, flops, overhead, label, dtype_name = make_workload(args.workload, args.n)
+    step, flops, overhead, label, dtype_name, outputs = make_workload(args.workload, args.n)
     dt, dt_ev = timed(step, args.steps, args.warmup)
+    if args.dump_outputs:  # (before the input is restored below: the restore overwrites the factorizations in place)
+        written = dump_outputs(args.dump_outputs, outputs(), f"_rank{rank}" if world > 1 else "")
+        if rank == 0:
+            print(f"bench: wrote {len(written)} output arrays to {args.dump_outputs}: {written}", file=sys.stderr, flush=True)
+    del outputs
     if overhead is not None:  # restoring the input is not part of the factorization
         odt, odt_ev = timed(overhead, args.steps, 1)
         dt, dt_ev = max(dt - odt, 1e-9), max(dt_ev - odt_ev, 1e-9)
@@ -508,7 +578,7 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = flops * world * args.steps / dt / 1e9  # whole-job GFLOP/s
     prof_main = None
-    if dist is None:
+    if dist is None and args.full:
         try:
             prof_main = profiled(step)
         except Exception:
@@ -517,13 +587,13 @@ def main():
     # ---- several GPUs, default run: the collective-free GEMM and the large block-cyclic LU ride along (all ranks take part),
     # and rank 0 times the single-GPU LU of the headline's size: the N = 1 point of the strong-scaling curve, same run
     multi_others, lu_1gpu = None, None
-    if dist is not None and defaulted and args.workload == "lu" and not args.no_extras:
+    if dist is not None and defaulted and args.workload == "lu" and args.full and not args.no_extras:
         multi_others = {}
         del step
         torch.cuda.empty_cache()
         for name, nn, reps, wu in (("gemm", 0, 10, 2), ("lu", 65536, 2, 1)):
             try:
-                st, fl, ov, lb, dn = make_workload(name, nn)
+                st, fl, ov, lb, dn, _ = make_workload(name, nn)
                 t, _ = timed(st, reps, wu)
                 if ov is not None:
                     t = max(t - timed(ov, reps, 1)[0], 1e-9)
@@ -541,7 +611,7 @@ def main():
         dist.barrier()
     # ---- the N = 1 point of a strong-scaling curve, measured in the SAME run: rank 0 times the single-GPU driver on the same
     # workload (lu / llt) and size while the others wait; `speedup_vs_1gpu_same_run` at top level
-    if dist is not None and args.workload in ("lu", "llt"):
+    if dist is not None and args.workload in ("lu", "llt") and args.full:
         if rank == 0:
             try:
                 torch.cuda.empty_cache()
@@ -608,16 +678,17 @@ def main():
         if "speedup_of_this_run" in lu_1gpu:
             out["speedup_vs_1gpu_same_run"] = lu_1gpu["speedup_of_this_run"]
     if rank == 0:
-        try:
-            # idle-chip hand-off between two workgroups.  It separated the pool's two kinds of boxes for most of
-            # round 5 and then read 0.39-0.42 us on boxes that ran LU in 104-105 ms and 0.58 us on one that ran it in 87.8: it does
-            # NOT classify a box.  What does is in the line already: others.*.roofline.dominant_kernel.chain_kernel.us_per_column,
-            # measured in the same run (LU leaf 3.0 against 3.85 us per column, Cholesky leaf 0.475 against 0.56-0.58; profiles/notes/DESIGN_history_r01_r05.md 6e)
-            out["xwg_hop_us"] = round(F.xwg_hop_us(2000), 3)
-        except Exception:
-            out["xwg_hop_us"] = None
+        if args.full:
+            try:
+                # idle-chip hand-off between two workgroups.  It separated the pool's two kinds of boxes for most of
+                # round 5 and then read 0.39-0.42 us on boxes that ran LU in 104-105 ms and 0.58 us on one that ran it in 87.8: it does
+                # NOT classify a box.  What does is in the line already: others.*.roofline.dominant_kernel.chain_kernel.us_per_column,
+                # measured in the same run (LU leaf 3.0 against 3.85 us per column, Cholesky leaf 0.475 against 0.56-0.58; profiles/notes/DESIGN_history_r01_r05.md 6e)
+                out["xwg_hop_us"] = round(F.xwg_hop_us(2000), 3)
+            except Exception:
+                out["xwg_hop_us"] = None
         # ---------------------------------------------------------------- roofline of the dominant kernel
-        if args.workload == "gemm":
+        if args.full and args.workload == "gemm":
             launch_s = dt_ev / args.steps  # one step == one launch of the MFMA GEMM kernel
             achieved = flops / launch_s / 1e12
             # HBM-side traffic needs the PMC counters (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes,
@@ -641,7 +712,7 @@ def main():
             if prof_main and prof_main["mfma_products"]["launches"]:
                 c0 = prof_main["mfma_products"]
                 out["roofline"]["launch_ms_single_profiled_launch"] = round(c0["ms"] / c0["launches"], 4)
-        elif args.workload == "qr":
+        elif args.full and args.workload == "qr":
             # HBM bound as specified: algorithmic bytes = the matrix read and written once
             gbs = 2.0 * 500000 * 256 * 4 / (dt / args.steps) / 1e9 if not args.n else None
             out["roofline"] = {"bound": "hbm", "achieved": round(gbs, 1) if gbs else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -652,7 +723,7 @@ def main():
                 out["roofline"]["dominant_kernel"] = kr
             else:
                 out["roofline"].update(dominant_from_profile("qr") or {})
-        else:
+        elif args.full:
             # the factorizations are chains of kernels: the whole-chain rate against the matrix-core peak of their trailing
             # updates; the dominant-kernel fields come from the committed kernel trace
             peak = FP64_MFMA_PEAK_TFLOPS if dtype_name == "f64" else FP32_MFMA_PEAK_TFLOPS
@@ -675,7 +746,7 @@ def main():
                 del a, b, c
 
         # ---------------------------------------------------------------- other hot-path workloads (one GPU)
-        if dist is None and not args.no_extras:
+        if args.full and dist is None and not args.no_extras:
             others = {}
             del step
             torch.cuda.empty_cache()
@@ -684,7 +755,7 @@ def main():
                 if name == args.workload or (only and name not in only.split(",")):
                     continue
                 try:
-                    st, fl, ov, lb, dn = make_workload(name)
+                    st, fl, ov, lb, dn, _ = make_workload(name)
                     if args.pause > 0:
                         # the chip leaves a long MFMA-bound run (the headline, LLT, LU) at reduced clocks for a while and the
                         # latency-bound workloads after it measured up to 40 % slower than on their own: every entry of
@@ -798,11 +869,12 @@ def main():
                 out["box_kind"] = None
 
         # ---------------------------------------------------------------- CPU baseline (oracle port, bounded sample)
-        if dist is None and not args.no_cpu:
+        if args.full and dist is None and not args.no_cpu:
             from oracle import oracle as orc
 
             ncpu = os.cpu_count() or 1
-            nthr = min(ncpu, 64)  # the port's column-parallel loops stop scaling well before 256 threads
+            # the port's column-parallel loops stop scaling well before 256 threads; a limit the environment already sets is kept
+            nthr = int(os.environ.get("OMP_NUM_THREADS") or 0) or min(ncpu, 64)
             os.environ["OMP_NUM_THREADS"] = str(nthr)
             rng = np.random.default_rng(0)
             hw = np.zeros((256, 256), order="F")

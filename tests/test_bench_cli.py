@@ -48,3 +48,58 @@ def test_source_wires_the_defaults_into_the_run():
     assert re.search(r'rccl = F\.RcclTransport\(', src) and "transport=rccl" in src
     assert '"scaling": "strong" if (args.workload in ("lu", "llt") and dist is not None) else "weak"' in src
     assert 'out["per_rank"] = per_rank' in src and "lu_1gpu_same_run" in src
+
+
+def test_cli_has_full_and_dump_outputs_and_checks_steps():
+    import subprocess
+
+    h = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, check=True).stdout
+    assert "--full" in h and "--dump-outputs DIR" in h
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    """what is not the headline (profiled repetition, roofline, `others`, CPU baselines, distributed extras) runs only with --full"""
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    for cond in ("if dist is None and args.full:", "if args.full and args.workload == \"gemm\":", "elif args.full and args.workload == \"qr\":",
+                 "elif args.full:", "if args.full and dist is None and not args.no_extras:", "if args.full and dist is None and not args.no_cpu:",
+                 "and args.full and not args.no_extras:", "if dist is not None and args.workload in (\"lu\", \"llt\") and args.full:"):
+        assert cond in src, cond
+
+
+def test_dump_outputs_whole_sampled_lower_and_budget(tmp_path):
+    import torch
+
+    big = torch.randn((2100, 3000), dtype=torch.float64, generator=torch.Generator().manual_seed(1)).t()  # column major, 50 MB
+    small = torch.randn((40, 100), dtype=torch.float32, generator=torch.Generator().manual_seed(2)).t()
+    spd = torch.randn((300, 300), dtype=torch.float64, generator=torch.Generator().manual_seed(3)).t()
+    perm = np.arange(2999, -1, -1, dtype=np.uint64)
+    outs = {"big": (big, False), "small": (small, False), "l": (spd, True), "perm": (perm, False), "big_lower": (big[:2100], True)}
+    w1 = bench.dump_outputs(str(tmp_path / "a"), outs)
+    w2 = bench.dump_outputs(str(tmp_path / "b"), outs)
+    assert w1 == w2 and sorted(w1) == ["big.npy", "big_lower.npy", "l.npy", "perm.npy", "small.npy"]
+    total = 0
+    for f in w1:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)  # same positions, same values
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.numpy())
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "a" / "l.npy"), np.tril(spd.numpy()))
+    assert np.array_equal(np.load(tmp_path / "a" / "perm.npy"), perm.astype(np.float64))
+    # a large output: DUMP_SAMPLE entries at the seeded positions, in column-major order
+    s = np.load(tmp_path / "a" / "big.npy")
+    assert s.shape == (bench.DUMP_SAMPLE,)
+    rng = np.random.default_rng(bench.DUMP_SEED)
+    i, j = rng.integers(0, 3000, bench.DUMP_SAMPLE), rng.integers(0, 2100, bench.DUMP_SAMPLE)
+    o = np.argsort(j * 3000 + i, kind="stable")
+    assert np.array_equal(s, big.numpy()[i[o], j[o]])
+    sl = np.load(tmp_path / "a" / "big_lower.npy")
+    bl = big[:2100].numpy()
+    rng = np.random.default_rng(bench.DUMP_SEED)  # every output draws its positions from the same seed
+    i, j = rng.integers(0, 2100, sl.size), rng.integers(0, 2100, sl.size)
+    i, j = np.maximum(i, j), np.minimum(i, j)
+    o = np.argsort(j * 2100 + i, kind="stable")
+    assert np.array_equal(sl, bl[i[o], j[o]])

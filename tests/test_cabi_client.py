@@ -4,48 +4,40 @@ tests/cabi_client/ref_client.c is written against the reference's own faer-ffi/f
 _Static_assert-ed against include/faer_hip.h, the `libfaer_v0_23_*` prototypes it calls are the reference's, and it
 links against libfaer_hip.so.  tests/cabi_client/hpp_client.cpp does the same through the reference's C++ wrapper
 faer-ffi/faer.hpp (v0_24 spelling + six-scalar dispatch tables => csrc/abi_compat.c).  Building needs the
-reference tree (here: /root/reference); the binaries land in tests/_build/cabi_client/ (git-ignored, they travel to
-the GPU box), where the -m gpu test runs them in `compute` mode."""
+reference tree (FAER_REFERENCE); the recipe is oracle/cabi_clients.py, the binaries land in oracle/_ref/cabi_client/
+(git-ignored, built by __graft_entry__.build()), where the host-only test runs them whether or not the reference is at hand
+and the -m gpu test runs them in `compute` mode."""
 import os
-import shutil
 import subprocess
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.environ.get("FAER_REFERENCE", "/root/reference")
-OUT = os.path.join(ROOT, "tests", "_build", "cabi_client")
 LIBDIR = os.path.join(ROOT, "faer-rs_amd")
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from oracle import cabi_clients  # noqa: E402
+
+OUT = cabi_clients.OUT
 
 
 def build_clients():
-    """returns the two binaries; raises CalledProcessError with the compiler output on a layout / prototype mismatch"""
-    ffi = os.path.join(REF, "faer-ffi")
-    os.makedirs(os.path.join(OUT, "hpp"), exist_ok=True)
-    rpath = "-Wl,-rpath,$ORIGIN/../../../faer-rs_amd"
-    ref_bin = os.path.join(OUT, "ref_client")
-    subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Werror", f"-I{ffi}", f"-I{os.path.join(ROOT, 'include')}",
-                    os.path.join(ROOT, "tests", "cabi_client", "ref_client.c"), "-o", ref_bin, f"-L{LIBDIR}", "-lfaer_hip", "-lm",
-                    rpath], check=True, capture_output=True, text=True)
-    # faer.hpp spells libfaer_v0_24_* but faer.h declares libfaer_v0_23_* (header drift in the reference): the C++
-    # client compiles against a GENERATED copy of faer.h with the v0_24 spelling (build directory only, never committed)
-    hdr = open(os.path.join(ffi, "faer.h")).read().replace("libfaer_v0_23_", "libfaer_v0_24_")
-    open(os.path.join(OUT, "hpp", "faer.h"), "w").write(hdr)
-    for f in ("faer.hpp", "quad.hpp"):
-        shutil.copyfile(os.path.join(ffi, f), os.path.join(OUT, "hpp", f))
-    hpp_bin = os.path.join(OUT, "hpp_client")
-    subprocess.run(["g++", "-std=c++20", "-O1", f"-I{os.path.join(OUT, 'hpp')}", os.path.join(ROOT, "tests", "cabi_client", "hpp_client.cpp"),
-                    "-o", hpp_bin, f"-L{LIBDIR}", "-lfaer_hip", rpath], check=True, capture_output=True, text=True)
-    shutil.rmtree(os.path.join(OUT, "hpp"))  # copies of reference sources do not stay around (nor travel)
-    return ref_bin, hpp_bin
+    """returns the two binaries (oracle/cabi_clients.build against the reference tree REF)"""
+    return cabi_clients.build(REF)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "faer-ffi", "faer.h")), reason="reference tree not available")
 def test_clients_compile_link_and_run_host_only():
-    try:
-        bins = build_clients()
-    except subprocess.CalledProcessError as e:  # show the compiler's message (e.g. the failing _Static_assert)
-        pytest.fail(e.stderr[-4000:])
+    """compiled and linked here when the reference tree is at hand, else the binaries __graft_entry__.build() made are run"""
+    bins = cabi_clients.binaries()
+    if os.path.exists(os.path.join(REF, "faer-ffi", "faer.h")):
+        try:
+            bins = build_clients()
+        except subprocess.CalledProcessError as e:  # show the compiler's message (e.g. the failing _Static_assert)
+            pytest.fail(e.stderr[-4000:])
+    elif not all(os.path.exists(b) for b in bins):
+        pytest.skip("neither the reference tree nor client binaries built by __graft_entry__.build() are available")
     for b in bins:
         r = subprocess.run([b], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr

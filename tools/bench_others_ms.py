@@ -1,4 +1,4 @@
-"""stdin: the JSON line of bench.py; prints the headline and the `ms` of every entry of `others` (A/B runs of bench options)"""
+"""stdin: the JSON line of `bench.py --full`; prints the headline and the `ms` of every entry of `others` (A/B runs of bench options)"""
 import json
 import sys
 
