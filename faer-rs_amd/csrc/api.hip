@@ -1414,10 +1414,9 @@ int faer_hip_debug_dist_two_streams_ok(size_t panel_rows, FaerHipDType dtype, in
 	return dist_two_streams_ok((idx_t) panel_rows, dtype == FaerHipDType_F64 ? 8 : 4, panel_cus, all_cus) ? 1 : 0;
 }
 void faer_hip_debug_lu_force_general(int on) { lu_force_general(on); }
-void faer_hip_debug_lend_cus(int on) { g_lend_cus.store(on); }
 void faer_hip_debug_lu_plan(size_t nb2_from, size_t pipe_from, size_t la_min_cols) { lu_debug_plan((long) nb2_from, (long) pipe_from, (long) la_min_cols); }
 long faer_hip_debug_qr_one_pass_columns(void) { return qr_last_one_pass_columns(); }
-void faer_hip_debug_qr_fused(int on) { tsqr_debug_fused(on); }
+void faer_hip_debug_qr_panel_copy(int on) { tsqr_debug_panel_copy(on); }
 void faer_hip_debug_qr_one_pass_f64(int on) { tsqr_debug_f64(on); }
 void faer_hip_debug_qr_panels_one_pass(int on) { tsqr_debug_panels(on); }
 void faer_hip_debug_qr_one_pass_shape_rule(long min_rows, long min_rows_per_column) { tsqr_debug_shape_rule(min_rows, min_rows_per_column); }

@@ -319,12 +319,6 @@ template <typename T> struct GemmExtra {
 	int k_trim = 0;
 	idx_t tri_skip = 0;
 	idx_t stair_nb = 0, stair_gap = 0, stair_row0 = 0;
-	// Lending idle CUs to a big product (128 x 128 pipelined tile): `ticket` = 8 zeroed device ints; the launch's tiles are then
-	// handed out through per-XCD counters (gemm.hip, GemmArgs::ticket).  helper_wgs == 0: the main launch; > 0: a HELPER launch
-	// of that many workgroups -- the same call with the same operands on another stream -- which takes tiles only while more
-	// than helper_margin remain in an XCD's share.  The caller orders consumers of dst behind BOTH launches.
-	int *ticket = nullptr;
-	int helper_wgs = 0, helper_margin = 0;
 	// short-wide / tall-narrow FULL output with a deep K (the V^H A product of a QR block application, 128 x n with K = rows): 128 x 128
 	// tiles with more K slices instead of the 64 x 64 tiles the tile-count rule picks (square QR N = 8192: -3 %, tools/gpu_qr_square_gemm_ab.py)
 	bool prefer_big_tiles = false;
@@ -352,13 +346,12 @@ std::vector<idx_t> llt_plan(idx_t n, idx_t tail_rows, idx_t nb2);
 int lu_leaf_width(idx_t m, int elem_bytes, int resident_workgroups);
 bool dist_two_streams_ok(idx_t panel_rows, int elem_bytes, int panel_cus, int all_cus);
 void lu_force_general(int on); // debug: every LU leaf on the non-cooperative path
-extern std::atomic<int> g_lend_cus; // faer_hip_debug_lend_cus: the look-ahead drivers lend the panel stream's idle CUs to their big products (ctx.hip; A/B, tests)
 void lu_debug_plan(long nb2_from, long pipe_from, long la_min); // debug: switch-over points of the look-ahead LU driver (0 = default)
 void lu_lend_copy(const void *device_copy, idx_t nrows, idx_t ncols, int elem_bytes); // the calling thread's next LU may restore A from it after an exchange timeout (getrf.hip)
 bool rccl_is_builtin_wait(FaerHipWaitFn fn); // rccl_transport.hip: is this the built-in transport's wait (takes any stream)
 bool loop_is_builtin_wait(FaerHipWaitFn fn); // loop_transport.hip: the loop-back transport of the tests (ranks = threads on one GPU)
 void level2_debug_force_memory_bodies(int on); // debug: tridiag / bidiag / Hessenberg vector kernels never keep their columns in registers
-void tsqr_debug_fused(int on); // debug: 0 = the one-pass QR runs update and Gram as separate launches (rounds 3-5), 1 = fused with look-ahead (default)
+void tsqr_debug_panel_copy(int on); // debug: 0 = the fp32 one-pass QR never keeps a raw copy of the panel (the path of matrices of more than 4.19 M rows), 1 = where it fits (default)
 void tsqr_debug_f64(int on); // debug: 0 = fp64 matrices never take the one-pass QR path
 void tsqr_debug_shape_rule(long min_rows, long min_aspect); // debug: shape rule of the whole-matrix one-pass QR path (0 = default)
 void tsqr_debug_panels(int on); // debug: 0 = the classic QR path never factors a panel on the one-pass path

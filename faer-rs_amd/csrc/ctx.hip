@@ -233,8 +233,6 @@ double xwg_hop_us(int iters)
 	return (double) ms * 1e3 / (2.0 * iters);
 }
 
-std::atomic<int> g_lend_cus{0}; // (measured: no gain, see potrf.hip / getrf.hip -- off by default)
-
 hipEvent_t Ctx::prof_event()
 {
 	if (!prof_pool.empty()) {

@@ -1573,8 +1573,8 @@ template long colpiv_qr_dev<float>(MatV<float>, MatV<float>, idx_t *, idx_t *);
 //                       of sym(A22) x -- the row sums tril(A22) x and the column sums striu(A22^H) x
 // History (N = 4096 fp64): rounds 2-5 read the triangle twice (a column pass that wrote back and a 16-row pass, each sum complete in
 // one wavefront / workgroup): 185 ms; cut into uniform pieces with partial sums added by the step kernel: 150 ms (the chip had waited
-// for the longest workgroup); one pass over tiles, the sums inside that pass behind a ticket (write-through + atomic, no fence): 140 ms
-// -- the tail "drain, ticket, reload, add" is four memory round trips in every launch; the sums as a launch of their own: 116 ms; loads
+// for the longest workgroup); one pass over tiles, the sums inside that pass behind an arrival counter (write-through + atomic, no fence): 140 ms
+// -- the tail "drain, count, reload, add" is four memory round trips in every launch; the sums as a launch of their own: 116 ms; loads
 // without branches, DPP column sums, a step kernel that holds its three columns in registers: 95 ms; the sums as helper blocks of the
 // step launch: 88 ms.  Running the vector phase in the last workgroup behind a release fence measured 2.4x slower in round 2 (an
 // agent-scope fence writes the L2 back).

@@ -20,7 +20,8 @@
 //           Below the top block the reflectors are V = P M: one more product, no reduction.
 //   y       D = R^-T C are the new top rows of X (= Q^T X), Y = R^-1 (V1 U)^-1 (D - X_top); below the top block the
 //           block reflector applied to X is X - P Y (the raw panel again, not V).
-//   update  X <- X - P Y and V = P M in ONE pass: rows are independent, so a wavefront maps ANY 32 rows to the 32
+//   update  X <- X - P Y and V = P M, fused with the next panel's Gram products (tq_fused_kernel); V = P M as a launch of its own
+//           (tq_form_v_kernel) where nothing else carries it: rows are independent, so a wavefront maps ANY 32 rows to the 32
 //           columns of a v_mfma_f32_32x32x2 tile -- each lane loads and stores 16-byte quads of its own rows straight
 //           from / to HBM, no LDS on the streamed side.
 //
@@ -1267,17 +1268,13 @@ template <typename T> __global__ __launch_bounds__(256) void tq_y_kernel(const T
 }
 
 // ------------------------------------------------------------------------------------------------
-// update: X <- X - P Y (columns [coff, coff + ts) of the trailing block) and, if do_v, V = P M over the panel
+// V = P M over the panel rows below its top block (stored over them)
 // ------------------------------------------------------------------------------------------------
-struct TqUpdArgs {
+struct TqFormVArgs {
 	float *P; // A[r1, c0], r1 = first row below the top block
-	float *X; // A[r1, cx + coff]
 	long ld;
-	int rows, w, ts; // rows from r1 down; strip width (<= 192)
-	const float *Yn;
-	int typ, coff;
+	int rows, w; // rows from r1 down
 	const float *Mn;
-	int do_v;
 	int nrb; // 128-row blocks
 	const int *stat;
 	int c0; // first column of the panel (tq_skip)
@@ -1326,45 +1323,32 @@ template <bool VEC> static __device__ __forceinline__ void tq_st4(float *col, in
 
 // One wavefront owns 128 rows: its 128 x 64 block of the panel is loaded ONCE into registers (32 quads per lane: lane
 // l & 31 holds rows 4 (l & 31) .. + 3 of column 2 i + (l >> 5) -- row slot q of the four interleaved 32-row tiles), then
-// 32-column strips of X stream through the accumulators: out(rows, j) = in(rows, j) + sum_k P(rows, k) Ys[k][j], and last
-// the two strips of V = P M, stored over the panel rows the wave has in registers.
-template <bool VEC> __global__ __launch_bounds__(256, 1) void tq_update_kernel(const TqUpdArgs a)
+// the two 32-column strips of V = P M are formed and stored over the panel rows the wave has in registers.
+template <bool VEC> __global__ __launch_bounds__(256, 1) void tq_form_v_kernel(const TqFormVArgs a)
 {
-	constexpr int PITCH = TQ_TS + 64;
-	__shared__ float Ys[64 * PITCH];
+	__shared__ float Ms[64 * 64];
 	if (tq_skip(a.stat, a.c0))
 		return;
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	{
-		// PITCH == 256 == the workgroup: thread c stages column c of Ys, row k per iteration -- 16 independent loads in flight per
-		// thread (one element per iteration was 64 dependent memory round trips at the head of every launch)
-		static_assert(PITCH == 256, "one thread per staged column");
-		const int c = tid;
-		const bool isy = c < a.ts, isv = c >= TQ_TS && a.do_v;
-		const float *src = isy ? a.Yn + a.coff + c : a.Mn + (c - TQ_TS);
-		const long step = isy ? (long) a.typ : 64L;
-#pragma unroll 1
-		for (int k0 = 0; k0 < 64; k0 += 16) {
-			float v[16];
+		// M (row major 64 x 64) as it is: 16 independent loads in flight per thread
+		float v[16];
 #pragma unroll
-			for (int u = 0; u < 16; ++u)
-				v[u] = (isy || isv) ? src[(long) (k0 + u) * step] : 0.f;
+		for (int u = 0; u < 16; ++u)
+			v[u] = a.Mn[u * 256 + tid];
 #pragma unroll
-			for (int u = 0; u < 16; ++u)
-				Ys[(k0 + u) * PITCH + c] = v[u];
-		}
+		for (int u = 0; u < 16; ++u)
+			Ms[u * 256 + tid] = v[u];
 	}
 	__syncthreads();
 	const int lam = lane & 31, h = lane >> 5;
-	const int nx = (a.ts + 31) >> 5;	   // 32-column strips of X
-	const int nv = a.do_v ? (a.w + 31) >> 5 : 0; // strips of V
+	const int nv = (a.w + 31) >> 5; // strips of V
 	for (int rbi = blockIdx.x * 4 + wv; rbi < a.nrb; rbi += gridDim.x * 4) {
 		// The row blocks are visited from the LAST one up, the Gram launches read from the first row down: each pass starts with what the
 		// pass before it touched last, i.e. with what the memory-side cache (256 MB) still holds
 		const int rb = a.nrb - 1 - rbi;
 		const int rows = a.rows - rb * 128; // valid rows from the block's first row (may exceed 128)
-		const float *Pb = a.P + (long) rb * 128;
-		float *Xb = a.X + (long) rb * 128;
+		float *Pb = a.P + (long) rb * 128;
 		f32x4 pr[32];
 #pragma unroll
 		for (int i = 0; i < 32; ++i) {
@@ -1373,43 +1357,19 @@ template <bool VEC> __global__ __launch_bounds__(256, 1) void tq_update_kernel(c
 			if (kc < a.w)
 				pr[i] = tq_ld4<VEC>(Pb + (long) kc * a.ld, lam, rows);
 		}
-		// one wavefront per SIMD (512 registers): the next strip of X is fetched while the matrix cores work on this one
-		// (two wavefronts per SIMD without the prefetch registers spill and measured 10 % slower)
-		f32x4 xn[16];
-#pragma unroll
-		for (int r = 0; r < 16; ++r) {
-			const int j = (r & 3) + 8 * (r >> 2) + 4 * h;
-			xn[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-			if (nx > 0 && j < a.ts)
-				xn[r] = tq_ld4<VEC>(Xb + (long) j * a.ld, lam, rows);
-		}
 #pragma unroll 1
-		for (int st = 0; st < nx + nv; ++st) {
-			const bool isv = st >= nx;
-			const int sc = isv ? st - nx : st;
-			const int lcol = (isv ? TQ_TS : 0) + 32 * sc;
-			const int nvalid = (isv ? a.w : a.ts) - 32 * sc;
-			float *dst = (isv ? a.P + (long) rb * 128 : Xb) + (long) (32 * sc) * a.ld;
+		for (int sc = 0; sc < nv; ++sc) {
+			const int nvalid = a.w - 32 * sc;
+			float *dst = Pb + (long) (32 * sc) * a.ld;
 			f32x16 acc[4];
 #pragma unroll
 			for (int r = 0; r < 16; ++r)
 #pragma unroll
 				for (int q = 0; q < 4; ++q)
-					acc[q][r] = isv ? 0.f : xn[r][q];
-			if (st + 1 < nx) {
-				const float *nxt = Xb + (long) (32 * (st + 1)) * a.ld;
-				const int nval = a.ts - 32 * (st + 1);
-#pragma unroll
-				for (int r = 0; r < 16; ++r) {
-					const int j = (r & 3) + 8 * (r >> 2) + 4 * h;
-					xn[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-					if (j < nval)
-						xn[r] = tq_ld4<VEC>(nxt + (long) j * a.ld, lam, rows);
-				}
-			}
+					acc[q][r] = 0.f;
 #pragma unroll
 			for (int i = 0; i < 32; ++i) {
-				const float a0 = Ys[(2 * i + h) * PITCH + lcol + lam];
+				const float a0 = Ms[(2 * i + h) * 64 + 32 * sc + lam];
 #pragma unroll
 				for (int q = 0; q < 4; ++q)
 					acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, pr[i][q], acc[q], 0, 0, 0);
@@ -2086,10 +2046,6 @@ template <> struct TqVec<double> {
 	typedef f64x2 v;
 	static constexpr int RPV = 2;
 };
-template <> struct TqVec<float> {
-	typedef f32x4 v;
-	static constexpr int RPV = 4;
-};
 
 template <typename T> struct TqGramTArgs {
 	const T *P; // A[r0, c0]
@@ -2579,15 +2535,17 @@ template <typename T, bool VEC> __global__ __launch_bounds__(512, 1) void tq_upd
 // ------------------------------------------------------------------------------------------------
 // driver
 // ------------------------------------------------------------------------------------------------
-static void tq_launch_update(bool vec, int nwg, const TqUpdArgs &ua)
+// V = P M over a panel: one persistent workgroup per CU of the `ncu` it may use (its registers and LDS allow no second one)
+static void tq_launch_form_v(bool vec, int ncu, const TqFormVArgs &va)
 {
 	hipStream_t s = ctx().stream;
-	// (profile class 2; algorithmic bytes of the launch: the panel and the strip read once, the strip -- and V, if stored -- written once)
-	ProfScope prof(2, (double) ua.rows * 4.0 * ((double) ua.w + 2.0 * (double) ua.ts + (ua.do_v ? (double) ua.w : 0.0)));
+	const int nwg = (va.nrb + 3) / 4 < ncu ? (va.nrb + 3) / 4 : ncu;
+	// (profile class 2; algorithmic bytes of the launch: the panel read once, V written once)
+	ProfScope prof(2, (double) va.rows * 4.0 * 2.0 * (double) va.w);
 	if (vec)
-		hipLaunchKernelGGL(tq_update_kernel<true>, dim3(nwg), dim3(256), 0, s, ua);
+		hipLaunchKernelGGL(tq_form_v_kernel<true>, dim3(nwg), dim3(256), 0, s, va);
 	else
-		hipLaunchKernelGGL(tq_update_kernel<false>, dim3(nwg), dim3(256), 0, s, ua);
+		hipLaunchKernelGGL(tq_form_v_kernel<false>, dim3(nwg), dim3(256), 0, s, va);
 }
 
 static void tq_gram(const float *P, const float *X, long ld, int rows, int w, int t, bool want_g, bool want_sq, bool vec, double *Gp, float *Cp,
@@ -2628,8 +2586,8 @@ static void tq_gram(const float *P, const float *X, long ld, int rows, int w, in
 	FH_HIP(hipGetLastError());
 }
 
-static std::atomic<int> g_tq_fused{1};
-void tsqr_debug_fused(int on) { g_tq_fused.store(on); }
+static std::atomic<int> g_tq_panel_copy{1};
+void tsqr_debug_panel_copy(int on) { g_tq_panel_copy.store(on); }
 
 static void tq_launch_fused(bool vec, int mode, int nwg, const TqFusedArgs &fa)
 {
@@ -2736,90 +2694,61 @@ bool tsqr_applicable(idx_t m, idx_t n, idx_t rs, idx_t cs, idx_t bs)
 	return bs % TQ_PW == 0 || TQ_PW % bs == 0;
 }
 
-// Factors the leading panels of A (m x n fp32, column major) on the one-pass path.  Returns the number of COLUMNS
-// completed (a multiple of 64, or n); the state is then that of the reference algorithm after those columns: R and
-// V in place, the T blocks in H, taus[j] = T_jj, every reflector applied to all columns on the right.
-// `reason` reports why it stopped early (TQ_FAIL_*).
-template <typename T> static idx_t tsqr_factor_plain(MatV<T> A, MatV<T> H, T *taus, int *reason, idx_t rows_above);
-
-idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t rows_above)
-{
-	// schedule 3 (faer_hip_debug_qr_fused): the plain schedule on the streaming kernels of the end of round 6 (tq_gramT_kernel /
-	// tq_updateT_kernel, written for fp64 data); needs 16-byte aligned columns
-	if (g_tq_fused.load() == 3 && A.cs % 4 == 0 && (uintptr_t) A.p % 16 == 0)
-		return tsqr_factor_plain<float>(A, H, taus, reason, rows_above);
-	const idx_t m = A.nrows, n = A.ncols, ld = A.cs, bs = H.nrows;
+// ------------------------------------------------------------------------------------------------
+// One call of either driver (tsqr_factor: fp32 data, fused schedule; tsqr_factor64: fp64 data, plain schedule): the workspace, the
+// launches in front of the first panel, the panel / y / cross-panel T launches and the status read-back.  The schedules stay in the drivers.
+// ------------------------------------------------------------------------------------------------
+template <typename T> struct TqWork {
+	MatV<T> A, H;
+	T *taus;
+	idx_t m = A.nrows, n = A.ncols, ld = A.cs, bs = H.nrows;
+	int npan = (int) ((n + TQ_PW - 1) / TQ_PW);
+	int ldc = ((int) n + 63) & ~63, typ = ldc, ldz = ldc;
 	hipStream_t s = ctx().stream;
-	const bool vec = (ld % 4 == 0) && ((uintptr_t) A.p % 16 == 0);
-	const int npan = (int) ((n + TQ_PW - 1) / TQ_PW);
-	const int ldc = ((int) n + 63) & ~63;
-	const int typ = ldc, ldz = ldc;
-	Scratch gp((size_t) TQ_NB * 4096 * 8), cp((size_t) TQ_NB * 64 * TQ_TS * 4), sp((size_t) TQ_NB * 256 * 4);
-	// fp64 workspace: G (NG x 4096), N1, N3, Gf (4096 each), C (NG x 64 x ldc), S (NG x 256; a second slab of that size is unused padding), abv (n + 64),
-	//                 Td, Md (npan x 4096 each), Z, B (npan x 64 x ldz each); then fp32: Mn (npan x 4096), top, A1s (4096 each), Yn (64 x typ); then the status words
-	const size_t nd = (size_t) TQ_NG * 4096 + 3 * 4096 + (size_t) TQ_NG * 64 * ldc + (size_t) 2 * TQ_NG * 256 + (size_t) n + 64 + (size_t) 2 * npan * 4096 +
-			  (size_t) 2 * npan * 64 * ldz;
-	Scratch small(nd * 8 + ((size_t) npan * 4096 + 2 * 4096 + (size_t) 64 * typ) * 4 + 2048);
-	double *G = small.as<double>();
-	double *N1 = G + (size_t) TQ_NG * 4096, *N3 = N1 + 4096, *Gf = N3 + 4096, *C = Gf + 4096;
-	double *S = C + (size_t) TQ_NG * 64 * ldc, *abv = S + (size_t) 2 * TQ_NG * 256;
-	double *Td = abv + n + 64, *Md = Td + (size_t) npan * 4096, *Z = Md + (size_t) npan * 4096, *Bx = Z + (size_t) npan * 64 * ldz;
-	float *Mn = reinterpret_cast<float *>(Bx + (size_t) npan * 64 * ldz); // one per panel: V of step k is formed beside panel k + 1
-	float *top = Mn + (size_t) npan * 4096;
-	float *A1s = top + 4096;
-	float *Yn = A1s + 4096;
-	int *stat = reinterpret_cast<int *>(Yn + (size_t) 64 * typ);
-	FH_HIP(hipMemsetAsync(stat, 0, 2048, s));
-	FH_HIP(hipMemsetAsync(abv, 0, (size_t) (n + 64) * 8, s));
-	if (rows_above > 0 && A.rs == 1)
-		hipLaunchKernelGGL(tq_above_kernel<float>, dim3((unsigned) n), dim3(256), 0, s, (const float *) A.p, (long) ld, (int) rows_above, abv);
-	const bool cross = bs > TQ_PW && npan > 1;
-	if (cross)
-		FH_HIP(hipMemsetAsync(Z, 0, (size_t) npan * 64 * ldz * 8, s));
-	const int ncu_all = ctx().stream_cus();
-	int cus_taken = 0; // CUs held by side-stream kernels while the persistent update kernels run
-	// two Gram workgroups per CU; a CU held by a side-stream kernel (its LDS leaves no room for one) would run its two AFTER the others
-	auto gram_nb = [&]() { return cus_taken > 0 && ncu_all - cus_taken > 8 ? 2 * (ncu_all - cus_taken) : TQ_NB; };
-	// Gram launches of panel [c0, c0 + w), rows from c0 down: G (want_g) and / or C against the columns [cx, cx + t) in strips
-	// of <= 192
-	auto launch_gram = [&](int c0, int w, bool want_g, int cx, int t, bool first, double *Sd) {
-		const float *P = A.p + (long) c0 * ld + c0;
-		const int rows = (int) (m - c0);
-		if (t == 0) {
-			if (want_g)
-				tq_gram(P, P, ld, rows, w, 0, true, first, vec, gp.as<double>(), cp.as<float>(), sp.as<float>(), G, C, ldc, 0, Sd, stat, c0, A1s, Gf, stat + 128, gram_nb());
-			return;
+	bool cross = bs > TQ_PW && npan > 1; // a block of Q_coeff spans several panels: cross-panel blocks of T
+	// partial sums of the Gram launches: G (fp64), C and the column squares (scalar type)
+	Scratch gp{(size_t) TQ_NB * 4096 * 8}, cp{(size_t) TQ_NB * 64 * TQ_TS * sizeof(T)}, sp{(size_t) TQ_NB * 256 * sizeof(T)};
+	// fp64: G (NG x 4096), N1, N3, Gf (4096 each), C (NG x 64 x ldc), S (two slabs of NG x 256), abv (n + 64), Td, Md (npan x 4096 each),
+	//       Z, B (npan x 64 x ldz each); then the scalar type: Mn (npan x 4096: V of step k may be formed beside panel k + 1), top, A1s
+	//       (4096 each), Yn (64 x typ); then the status words
+	Scratch small{((size_t) TQ_NG * 4096 + 3 * 4096 + (size_t) TQ_NG * 64 * ldc + (size_t) 2 * TQ_NG * 256 + (size_t) n + 64 + (size_t) 2 * npan * 4096 +
+		       (size_t) 2 * npan * 64 * ldz) * 8 +
+		      ((size_t) npan * 4096 + 2 * 4096 + (size_t) 64 * typ) * sizeof(T) + 2048};
+	double *G, *N1, *N3, *Gf, *C, *S, *abv, *Td, *Md, *Z, *Bx;
+	T *Mn, *top, *A1s, *Yn;
+	int *stat;
+
+	// zeroes the status words, abv and Z; the squares of the rows above the block (a panel of the classic path), the range guard of the
+	// columns the first step's Gram launches do not cover
+	TqWork(MatV<T> A_, MatV<T> H_, T *taus_, idx_t rows_above) : A(A_), H(H_), taus(taus_)
+	{
+		// (the streaming kernels load down the columns: tsqr_applicable / tsqr_applicable64 / tsqr_panel_applicable admit nothing else)
+		FH_CHECK(A.rs == 1, "tsqr: unit row stride");
+		G = small.as<double>();
+		N1 = G + (size_t) TQ_NG * 4096, N3 = N1 + 4096, Gf = N3 + 4096, C = Gf + 4096;
+		S = C + (size_t) TQ_NG * 64 * ldc, abv = S + (size_t) 2 * TQ_NG * 256;
+		Td = abv + n + 64, Md = Td + (size_t) npan * 4096, Z = Md + (size_t) npan * 4096, Bx = Z + (size_t) npan * 64 * ldz;
+		Mn = reinterpret_cast<T *>(Bx + (size_t) npan * 64 * ldz), top = Mn + (size_t) npan * 4096, A1s = top + 4096, Yn = A1s + 4096;
+		stat = reinterpret_cast<int *>(Yn + (size_t) 64 * typ);
+		FH_HIP(hipMemsetAsync(stat, 0, 2048, s));
+		FH_HIP(hipMemsetAsync(abv, 0, (size_t) (n + 64) * 8, s));
+		if (rows_above > 0)
+			hipLaunchKernelGGL(tq_above_kernel<T>, dim3((unsigned) n), dim3(256), 0, s, (const T *) A.p, (long) ld, (int) rows_above, abv);
+		if (cross)
+			FH_HIP(hipMemsetAsync(Z, 0, (size_t) npan * 64 * ldz * 8, s));
+		if (n > TQ_PW + TQ_TS) {
+			hipLaunchKernelGGL(tq_range_rest_kernel<T>, dim3((unsigned) (n - (TQ_PW + TQ_TS))), dim3(256), 0, s, A.p, (long) ld, (int) m, TQ_PW + TQ_TS, stat);
+			FH_HIP(hipGetLastError());
 		}
-		for (int off = 0; off < t; off += TQ_TS) {
-			const int ts = t - off < TQ_TS ? t - off : TQ_TS;
-			// the range guard of these launches covers the first strip only (n <= 256); tq_range_rest_kernel checks the others
-			tq_gram(P, A.p + (long) (cx + off) * ld + c0, ld, rows, w, ts, want_g && off == 0, first && off == 0, vec, gp.as<double>(),
-				cp.as<float>(), sp.as<float>(), G, C, ldc, cx + off - (c0 + w), Sd, stat, c0, A1s, Gf, stat + 128, gram_nb());
-		}
-	};
-	auto tx_args = [&]() {
-		TqTxArgs<float> ta;
-		ta.A = A.p;
-		ta.ld = ld;
-		ta.n = (int) n;
-		ta.bs = (int) bs;
-		ta.Td = Td;
-		ta.Md = Md;
-		ta.Z = Z;
-		ta.ldz = ldz;
-		ta.B = Bx;
-		ta.H = H.p;
-		ta.hrs = H.rs;
-		ta.hcs = H.cs;
-		ta.stat = stat;
-		ta.stage = 0;
-		return ta;
-	};
-	auto launch_panel = [&](int k, hipStream_t ps) {
-		const int c0 = k * TQ_PW;
-		const int w = (int) (n - c0 < TQ_PW ? n - c0 : TQ_PW);
-		const int t = (int) n - c0 - w;
-		TqPanelArgs<float> pa;
+	}
+
+	int width(int k) const { return (int) (n - k * TQ_PW < TQ_PW ? n - k * TQ_PW : TQ_PW); }
+
+	// the panel kernel of panel k (one workgroup)
+	void launch_panel(int k) const
+	{
+		const int c0 = k * TQ_PW, w = width(k), t = (int) n - c0 - w;
+		TqPanelArgs<T> pa;
 		pa.A = A.p;
 		pa.ld = ld;
 		pa.m = (int) m;
@@ -2846,15 +2775,153 @@ idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t 
 		pa.taus = taus;
 		pa.stat = stat;
 		pa.dbg = reinterpret_cast<long long *>(stat + 16);
-		StreamScope psc(ps);
 		ProfScope prof(4, 1.0);
-		hipLaunchKernelGGL(tq_panel_kernel<float>, dim3(1), dim3(TQ_PT), 0, ps, pa);
+		hipLaunchKernelGGL(tq_panel_kernel<T>, dim3(1), dim3(TQ_PT), 0, s, pa);
+	}
+
+	// the y kernel of step k (Sr: the column squares its first launch checks), or behind the last panel the store of its top block
+	void launch_y(int k, const double *Sr) const
+	{
+		const int c0 = k * TQ_PW, w = width(k), t = (int) n - c0 - w;
+		if (t == 0) {
+			hipLaunchKernelGGL(tq_top_kernel<T>, dim3(1), dim3(256), 0, s, A.p, (long) ld, c0, c0, w, (const T *) top, (const int *) stat);
+			return;
+		}
+		TqYArgs<T> ya;
+		ya.A = A.p;
+		ya.ld = ld;
+		ya.r0 = c0;
+		ya.cx = c0 + w;
+		ya.w = w;
+		ya.t = t;
+		ya.C = C;
+		ya.ldc = ldc;
+		ya.N1 = N1;
+		ya.N3 = N3;
+		ya.Md = Md + (size_t) k * 4096;
+		ya.abv = abv;
+		ya.Yn = Yn;
+		ya.typ = typ;
+		ya.Z = Z + (size_t) k * 64 * ldz;
+		ya.ldz = ldz;
+		ya.top = top;
+		ya.stat = stat;
+		ya.Sr = Sr;
+		ya.check_range = k == 0;
+		ya.range_cols = t < TQ_TS ? t : TQ_TS;
+		ya.mrows = (int) m;
+		hipLaunchKernelGGL(tq_y_kernel<T>, dim3((t + 15) / 16), dim3(256), 0, s, ya);
+	}
+
+	TqTxArgs<T> tx_args(int stage) const
+	{
+		TqTxArgs<T> ta;
+		ta.A = A.p;
+		ta.ld = ld;
+		ta.n = (int) n;
+		ta.bs = (int) bs;
+		ta.Td = Td;
+		ta.Md = Md;
+		ta.Z = Z;
+		ta.ldz = ldz;
+		ta.B = Bx;
+		ta.H = H.p;
+		ta.hrs = H.rs;
+		ta.hcs = H.cs;
+		ta.stat = stat;
+		ta.stage = stage;
+		return ta;
+	}
+
+	// stage 1 or 2 of the cross-panel T blocks on the side stream, behind everything issued so far
+	void launch_tx_stage(const TqSide &side, int stage) const
+	{
+		FH_HIP(hipEventRecord(side.xfork, s));
+		FH_HIP(hipStreamWaitEvent(side.tx, side.xfork, 0));
+		hipLaunchKernelGGL(tq_tx_kernel<T>, dim3(npan - 1), dim3(256), 0, side.tx, tx_args(stage));
+	}
+
+	// the cross-panel T blocks: the side stream's stages waited for (on_side), or formed now on the call's stream
+	void finish_tx(const TqSide &side, bool on_side) const
+	{
+		if (!cross)
+			return;
+		if (on_side) {
+			FH_HIP(hipEventRecord(side.xdone, side.tx));
+			FH_HIP(hipStreamWaitEvent(s, side.xdone, 0));
+		} else if (bs <= (TQ_TX_MAXL + 1) * TQ_PW) {
+			hipLaunchKernelGGL(tq_tx_kernel<T>, dim3(npan - 1), dim3(256), 0, s, tx_args(0));
+		} else {
+			hipLaunchKernelGGL(tq_tx_general_kernel<T>, dim3(npan - 1), dim3(256), 0, s, tx_args(0));
+		}
+		FH_HIP(hipGetLastError());
+	}
+
+	// waits for the call's stream; the columns completed (n, or where a panel stopped it: *reason says why)
+	idx_t columns_done(int *reason) const
+	{
+		int *st = ctx().pinned_ints(); // (a pageable target makes the copy a staged, blocking one)
+		FH_HIP(hipMemcpyAsync(st, stat, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+		FH_HIP(hipStreamSynchronize(s));
+#ifdef FH_TQ_TIMING
+		{
+			long long d[32];
+			FH_HIP(hipMemcpy(d, stat + 16, sizeof(d), hipMemcpyDeviceToHost));
+			fprintf(stderr, "tq_panel phases (shader cycles): start %lld: load %lld chol %lld reload %lld lu %lld finish %lld tests %lld out %lld M %lld T %lld\n",
+				d[0], d[1] - d[0], d[2] - d[1], 0LL, d[3] - d[2], d[4] - d[3], d[5] - d[4], d[6] - d[5], d[7] - d[6], d[8] - d[7]);
+			fprintf(stderr, "  load: range %lld loads %lld barrier %lld fill %lld | U, U^-1, V1^-1: %lld | A iterations:", d[12] - d[0], d[13] - d[12], d[14] - d[13], d[1] - d[14], d[15] - d[3]);
+			for (int i = 0; i < 7; ++i)
+				fprintf(stderr, " %lld", d[17 + i] - d[16 + i]);
+			fprintf(stderr, " | B iterations:");
+			for (int i = 0; i < 7; ++i)
+				fprintf(stderr, " %lld", d[25 + i] - d[24 + i]);
+			fprintf(stderr, "\n");
+			double res[3];
+			memcpy(res, d + 9, sizeof(res));
+			fprintf(stderr, "tq_panel residuals of the last panel: |V1 V1^-1 - I| %.3e  |U U^-1 - I| %.3e  |R~ R~^-1 - I| %.3e\n", res[0], res[1], res[2]);
+		}
+#endif
+		*reason = st[0] ? st[2] : TQ_OK;
+		return st[0] ? (idx_t) st[1] : n;
+	}
+};
+
+// Factors the leading panels of A (m x n fp32, column major) on the one-pass path.  Returns the number of COLUMNS
+// completed (a multiple of 64, or n); the state is then that of the reference algorithm after those columns: R and
+// V in place, the T blocks in H, taus[j] = T_jj, every reflector applied to all columns on the right.
+// `reason` reports why it stopped early (TQ_FAIL_*).
+idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t rows_above)
+{
+	const TqWork<float> q(A, H, taus, rows_above);
+	const idx_t m = q.m, n = q.n, ld = q.ld;
+	const int npan = q.npan;
+	hipStream_t s = q.s;
+	const bool vec = (ld % 4 == 0) && ((uintptr_t) A.p % 16 == 0);
+	const int ncu_all = ctx().stream_cus();
+	int cus_taken = 0; // CUs held by side-stream kernels while the persistent update kernels run
+	// two Gram workgroups per CU; a CU held by a side-stream kernel (its LDS leaves no room for one) would run its two AFTER the others
+	auto gram_nb = [&]() { return cus_taken > 0 && ncu_all - cus_taken > 8 ? 2 * (ncu_all - cus_taken) : TQ_NB; };
+	// Gram launches of panel [c0, c0 + w), rows from c0 down: G (want_g) and / or C against the columns [cx, cx + t) in strips
+	// of <= 192
+	auto launch_gram = [&](int c0, int w, bool want_g, int cx, int t, bool first, double *Sd) {
+		const float *P = A.p + (long) c0 * ld + c0;
+		const int rows = (int) (m - c0);
+		if (t == 0) {
+			if (want_g)
+				tq_gram(P, P, ld, rows, w, 0, true, first, vec, q.gp.as<double>(), q.cp.as<float>(), q.sp.as<float>(), q.G, q.C, q.ldc, 0, Sd, q.stat, c0, q.A1s,
+					q.Gf, q.stat + 128, gram_nb());
+			return;
+		}
+		for (int off = 0; off < t; off += TQ_TS) {
+			const int ts = t - off < TQ_TS ? t - off : TQ_TS;
+			// the range guard of these launches covers the first strip only (n <= 256); tq_range_rest_kernel checks the others
+			tq_gram(P, A.p + (long) (cx + off) * ld + c0, ld, rows, w, ts, want_g && off == 0, first && off == 0, vec, q.gp.as<double>(), q.cp.as<float>(),
+				q.sp.as<float>(), q.G, q.C, q.ldc, cx + off - (c0 + w), Sd, q.stat, c0, q.A1s, q.Gf, q.stat + 128, gram_nb());
+		}
 	};
-	// one block of Q_coeff over all panels (the tall-skinny case): the cross-panel blocks of T in two stages beside the last steps
-	const bool fused = g_tq_fused.load() != 0;
 	// raw copy of the current panel below its top block for the U2 launches (see there); not for matrices where it would exceed 1 GiB
 	const long ldpc = (long) ((m + 63) & ~(idx_t) 63);
-	const bool want_copy = fused && g_tq_fused.load() != 2 && npan > 2 && (size_t) ldpc * TQ_PW * sizeof(float) <= ((size_t) 1 << 30);
+	const bool want_copy = g_tq_panel_copy.load() != 0 && npan > 2 && (size_t) ldpc * TQ_PW * sizeof(float) <= ((size_t) 1 << 30);
 	struct OptScratch {
 		void *p = nullptr;
 		~OptScratch()
@@ -2866,50 +2933,38 @@ idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t 
 	} pcopy;
 	if (want_copy)
 		pcopy.p = ctx().alloc((size_t) ldpc * TQ_PW * sizeof(float));
-	const bool two_stage = cross && bs >= n && bs <= (TQ_TX_MAXL + 1) * TQ_PW && npan >= 2;
+	// one block of Q_coeff over all panels (the tall-skinny case): the cross-panel blocks of T in two stages beside the last steps
+	const bool two_stage = q.cross && q.bs >= n && q.bs <= (TQ_TX_MAXL + 1) * TQ_PW && npan >= 2;
 	// look-ahead: the columns of the next panel are updated first, its Gram matrix and its panel kernel (ONE workgroup, ~110 us)
-	// follow at once, and the rest of the update + the products against the next panel run beside that kernel.  It is on where
-	// the rest of the update is long enough to cover what the panel kernel loses beside streaming kernels (>= 192 more trailing
-	// columns).  Two variants that forced it (always / a split Gram launch beside the panel kernel) measured slower and are
-	// gone: profiles/r03_qr_lookahead.txt keeps the record.
+	// follow at once, and the rest of the update + the products against the next panel run beside that kernel.  Variants that forced
+	// it (always / a split Gram launch beside the panel kernel) measured slower and are gone: profiles/r03_qr_lookahead.txt keeps the record.
 	const TqSide side = tq_side();
 	bool tx_on_side = false;
 	bool panel_on_side = false;
-	// Gram products and panel kernel of panel p
-	auto gram_and_panel = [&](int p, bool first) {
-		const int pc0 = p * TQ_PW;
-		const int pw = (int) (n - pc0 < TQ_PW ? n - pc0 : TQ_PW);
-		const int pt = (int) n - pc0 - pw;
-		launch_gram(pc0, pw, true, pc0 + pw, pt, first, S);
-		launch_panel(p, s);
-	};
-	if (n > TQ_PW + TQ_TS) {
-		hipLaunchKernelGGL(tq_range_rest_kernel<float>, dim3((unsigned) (n - (TQ_PW + TQ_TS))), dim3(256), 0, s, A.p, (long) ld, (int) m, TQ_PW + TQ_TS, stat);
-		FH_HIP(hipGetLastError());
-	}
-	double *Sy = S; // the column squares the first y kernel checks
-	if (fused && n > TQ_PW) {
+	double *Sy = q.S; // the column squares the first y kernel checks
+	if (n > TQ_PW) {
 		// the first panel's kernel needs G only: the products against the trailing columns (most of the first Gram launch: 190 us) run on
 		// the side stream beside it; their column squares go to the second slab of S
 		const int w0 = TQ_PW, t0 = (int) n - TQ_PW;
-		launch_gram(0, w0, true, w0, 0, true, S);
+		launch_gram(0, w0, true, w0, 0, true, q.S);
 		FH_HIP(hipEventRecord(side.pfork, s));
 		FH_HIP(hipStreamWaitEvent(side.panel, side.pfork, 0));
 		cus_taken += 1;
 		{
 			StreamScope sc(side.panel);
-			Sy = S + (size_t) TQ_NG * 256;
+			Sy = q.S + (size_t) TQ_NG * 256;
 			launch_gram(0, w0, false, w0, t0, true, Sy);
 			FH_HIP(hipEventRecord(side.pdone, side.panel));
 		}
-		launch_panel(0, s);
+		q.launch_panel(0);
 		panel_on_side = true;
 	} else {
-		gram_and_panel(0, true);
+		launch_gram(0, (int) n, true, (int) n, 0, true, q.S);
+		q.launch_panel(0);
 	}
 	for (int k = 0; k < npan; ++k) {
 		const int c0 = k * TQ_PW;
-		const int w = (int) (n - c0 < TQ_PW ? n - c0 : TQ_PW);
+		const int w = q.width(k);
 		const int t = (int) n - c0 - w;
 		const int wn = t < TQ_PW ? t : TQ_PW; // width of the next panel
 		if (panel_on_side) {
@@ -2917,104 +2972,24 @@ idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t 
 			panel_on_side = false;
 			cus_taken -= 1;
 		}
-		if (t > 0) {
-			TqYArgs<float> ya;
-			ya.A = A.p;
-			ya.ld = ld;
-			ya.r0 = c0;
-			ya.cx = c0 + w;
-			ya.w = w;
-			ya.t = t;
-			ya.C = C;
-			ya.ldc = ldc;
-			ya.N1 = N1;
-			ya.N3 = N3;
-			ya.Md = Md + (size_t) k * 4096;
-			ya.abv = abv;
-			ya.Yn = Yn;
-			ya.typ = typ;
-			ya.Z = Z + (size_t) k * 64 * ldz;
-			ya.ldz = ldz;
-			ya.top = top;
-			ya.stat = stat;
-			ya.Sr = Sy;
-			ya.check_range = k == 0;
-			ya.range_cols = t < TQ_TS ? t : TQ_TS;
-			ya.mrows = (int) m;
-			hipLaunchKernelGGL(tq_y_kernel<float>, dim3((t + 15) / 16), dim3(256), 0, s, ya);
-		} else {
-			hipLaunchKernelGGL(tq_top_kernel<float>, dim3(1), dim3(256), 0, s, A.p, ld, c0, c0, w, top, stat);
-		}
-		if (two_stage && k == npan - 1 && tx_on_side) {
-			// stage 2 needs this panel's kernel and the V rows the last update wrote: beside the update below
-			TqTxArgs<float> t2 = tx_args();
-			t2.stage = 2;
-			FH_HIP(hipEventRecord(side.xfork, s));
-			FH_HIP(hipStreamWaitEvent(side.tx, side.xfork, 0));
-			hipLaunchKernelGGL(tq_tx_kernel<float>, dim3(npan - 1), dim3(256), 0, side.tx, t2);
-		}
+		q.launch_y(k, Sy);
+		if (two_stage && k == npan - 1 && tx_on_side)
+			q.launch_tx_stage(side, 2); // (it needs this panel's kernel and the V rows the last update wrote: beside the update below)
 		const int r1 = c0 + w;
 		const int rows = (int) (m - r1);
-		TqUpdArgs ua;
-		ua.ld = ld;
-		ua.rows = rows;
-		ua.w = w;
-		ua.Yn = Yn;
-		ua.typ = typ;
-		ua.Mn = Mn + (size_t) k * 4096;
-		ua.nrb = (rows + 127) / 128;
-		ua.stat = stat;
-		ua.c0 = c0;
-		ua.P = A.p + (long) c0 * ld + r1;
 		const bool v2 = vec && r1 % 4 == 0;
-		// columns [from, to) of the trailing matrix in strips of <= 192; with_v: V = P M afterwards (it overwrites the panel:
-		// in the same launch only when no other launch still reads the panel)
-		auto update = [&](int from, int to, bool with_v) {
+		// V = P M as a launch of its own (it overwrites the panel); the side-stream kernels keep their CUs
+		auto form_v = [&]() {
 			if (rows <= 0)
 				return;
-			// one persistent workgroup per CU (its registers and LDS allow no second one): 256 measured 5 % ahead of 512 and
-			// 10 % ahead of 1024 workgroups on the 5e5 x 256 factorization; the side-stream kernels keep their CUs
-			int nwg = (ua.nrb + 3) / 4;
-			const int ncu = ncu_all - cus_taken > 8 ? ncu_all - cus_taken : ncu_all;
-			if (nwg > ncu)
-				nwg = ncu;
-			const int nstrip = (to - from + TQ_TS - 1) / TQ_TS;
-			for (int st = 0; st < nstrip; ++st) {
-				ua.coff = from + st * TQ_TS;
-				ua.ts = to - ua.coff < TQ_TS ? to - ua.coff : TQ_TS;
-				ua.X = A.p + (long) (c0 + w + ua.coff) * ld + r1;
-				ua.do_v = with_v && nstrip == 1;
-				tq_launch_update(v2, nwg, ua);
-			}
-			if (with_v && nstrip != 1) {
-				ua.coff = 0;
-				ua.ts = 0;
-				ua.X = ua.P;
-				ua.do_v = 1;
-				tq_launch_update(v2, nwg, ua);
-			}
+			const TqFormVArgs va{A.p + (long) c0 * ld + r1, (long) ld, rows, w, q.Mn + (size_t) k * 4096, (rows + 127) / 128, q.stat, c0};
+			tq_launch_form_v(v2, ncu_all - cus_taken > 8 ? ncu_all - cus_taken : ncu_all, va);
 		};
-		// everything of the cross-panel T blocks that does not depend on the last panel's kernel: beside the Gram / reduce / panel
-		// kernels of the last panel (a single workgroup busy most of that time), one CU per panel.  The fork is recorded BEHIND the
-		// update of step npan - 2 and IN FRONT of the last panel's launches (rounds 3-5 recorded it behind them: the stage then ran
-		// beside the last update and the factorization ended with ~110 us of three workgroups)
-		auto tx_stage1 = [&]() {
-			if (!(two_stage && k == npan - 2))
-				return;
-			TqTxArgs<float> t1 = tx_args();
-			t1.stage = 1;
-			FH_HIP(hipEventRecord(side.xfork, s));
-			FH_HIP(hipStreamWaitEvent(side.tx, side.xfork, 0));
-			hipLaunchKernelGGL(tq_tx_kernel<float>, dim3(npan - 1), dim3(256), 0, side.tx, t1);
-			tx_on_side = true;
-			if (ncu_all > 8 * npan)
-				cus_taken += npan - 1;
-		};
-		if (fused && t > 0) {
+		if (t > 0) {
 			// ---- round 6: update + Gram in one pass, the next panel's kernel beside the second half
 			const int nchunks = (rows + 63) / 64;
 			TqFusedArgs fa;
-			fa.P = ua.P;
+			fa.P = A.p + (long) c0 * ld + r1;
 			fa.N = A.p + (long) (c0 + w) * ld + r1;
 			fa.F = fa.N;
 			fa.ld = ld;
@@ -3027,21 +3002,21 @@ idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t 
 			// V overwrites the panel, which the U2 launches read again: U1 leaves them a copy of the raw rows (one more write of 64
 			// columns; a separate V launch behind U2 costs a read and a write and ran beside the next step's first kernels: the y kernel
 			// 17 -> 80 us, U1 114 -> 180 us)
-			const bool copyp = t - wn > 0 && pcopy.p != nullptr;
+			const bool copyp = t - wn > 0 && pcopy.p;
 			fa.do_v = t - wn == 0 || copyp;
 			fa.Pc = copyp ? pcopy.f() : nullptr;
 			fa.ldpc = ldpc;
 			fa.want_g = 1;
-			fa.Yn = Yn;
-			fa.typ = typ;
+			fa.Yn = q.Yn;
+			fa.typ = q.typ;
 			fa.fo = 0;
-			fa.Mn = Mn + (size_t) k * 4096;
-			fa.Gp = gp.as<double>();
-			fa.Cp = cp.as<float>();
+			fa.Mn = q.Mn + (size_t) k * 4096;
+			fa.Gp = q.gp.as<double>();
+			fa.Cp = q.cp.as<float>();
 			fa.tp = 0;
 			fa.nchunks = nchunks;
-			fa.A1s = A1s;
-			fa.stat = stat;
+			fa.A1s = q.A1s;
+			fa.stat = q.stat;
 			fa.c0 = c0;
 			auto grid = [&]() { // two workgroups per CU
 				const int ncu = ncu_all - cus_taken > 8 ? ncu_all - cus_taken : ncu_all;
@@ -3051,8 +3026,8 @@ idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t 
 			// U1: the next panel's columns, its Gram matrix, V = P M
 			int nb = grid();
 			tq_launch_fused(v2, 1, nb, fa);
-			hipLaunchKernelGGL(tq_reduce_kernel<float>, dim3(4096 / 256, TQ_NG), dim3(256), 0, s, fa.Gp, fa.Cp, sp.as<float>(), nb, 0, 1, 0, G, C, ldc, 0, S, stat, nc0, Gf,
-					   stat + 128);
+			hipLaunchKernelGGL(tq_reduce_kernel<float>, dim3(4096 / 256, TQ_NG), dim3(256), 0, s, fa.Gp, fa.Cp, q.sp.as<float>(), nb, 0, 1, 0, q.G, q.C, q.ldc, 0, q.S, q.stat, nc0,
+					   q.Gf, q.stat + 128);
 			if (t - wn > 0) {
 				// U2 (side stream): the columns behind it and C'; the next panel's kernel runs on the main stream meanwhile
 				FH_HIP(hipEventRecord(side.pfork, s));
@@ -3074,83 +3049,41 @@ idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t 
 						fa.F = A.p + (long) (nc0 + wn + fo) * ld + r1;
 						nb = grid();
 						tq_launch_fused(v2, 2, nb, fa);
-						hipLaunchKernelGGL(tq_reduce_kernel<float>, dim3((64 * fa.tp + 255) / 256, TQ_NG), dim3(256), 0, side.panel, fa.Gp, fa.Cp, sp.as<float>(), nb,
-								   fa.tp, 0, 0, G, C, ldc, fo, S, stat, nc0, Gf, stat + 128);
+						hipLaunchKernelGGL(tq_reduce_kernel<float>, dim3((64 * fa.tp + 255) / 256, TQ_NG), dim3(256), 0, side.panel, fa.Gp, fa.Cp, q.sp.as<float>(), nb,
+								   fa.tp, 0, 0, q.G, q.C, q.ldc, fo, q.S, q.stat, nc0, q.Gf, q.stat + 128);
 					}
 					FH_HIP(hipEventRecord(side.pdone, side.panel));
 					// V = P M once nothing reads the panel any more: behind U2 on the side stream, beside the next step's first
 					// launches (nothing waits for it before the end of the factorization or the cross-panel T blocks)
 					// (only without the raw copy: matrices too tall for it)
 					if (!copyp)
-						update(0, 0, true);
+						form_v();
 				}
 				panel_on_side = true; // (here: U2 is what runs on the side stream)
 			}
-			tx_stage1(); // (k == npan - 2: on the side stream, beside the last panel's kernel)
-			launch_panel(k + 1, s);
-		} else if (t == 0) {
-			update(0, 0, true);
-		} else if (t - wn < TQ_TS) {
-			update(0, t, true);
-			tx_stage1();
-			gram_and_panel(k + 1, false);
+			// everything of the cross-panel T blocks that does not depend on the last panel's kernel: beside the Gram / reduce / panel
+			// kernels of the last panel (a single workgroup busy most of that time), one CU per panel.  The fork is recorded BEHIND the
+			// update of step npan - 2 and IN FRONT of the last panel's launches (rounds 3-5 recorded it behind them: the stage then ran
+			// beside the last update and the factorization ended with ~110 us of three workgroups)
+			if (two_stage && k == npan - 2) {
+				q.launch_tx_stage(side, 1);
+				tx_on_side = true;
+				if (ncu_all > 8 * npan)
+					cus_taken += npan - 1;
+			}
+			q.launch_panel(k + 1);
 		} else {
-			update(0, wn, false);
-			launch_gram(c0 + w, wn, true, c0 + w + wn, 0, false, S);
-			FH_HIP(hipEventRecord(side.pfork, s));
-			FH_HIP(hipStreamWaitEvent(side.panel, side.pfork, 0));
-			launch_panel(k + 1, side.panel);
-			FH_HIP(hipEventRecord(side.pdone, side.panel));
-			panel_on_side = true;
-			cus_taken += 1;
-			update(wn, t, true);
-			launch_gram(c0 + w, wn, false, c0 + w + wn, t - wn, false, S);
-		}
-		if (!tx_on_side)
-			tx_stage1(); // (the look-ahead branch: behind its last launch, as before)
-		FH_HIP(hipGetLastError());
-	}
-	if (cross) {
-		TqTxArgs<float> ta = tx_args();
-		if (tx_on_side) {
-			FH_HIP(hipEventRecord(side.xdone, side.tx));
-			FH_HIP(hipStreamWaitEvent(s, side.xdone, 0));
-		} else if (bs <= (TQ_TX_MAXL + 1) * TQ_PW) {
-			hipLaunchKernelGGL(tq_tx_kernel<float>, dim3(npan - 1), dim3(256), 0, s, ta);
-		} else {
-			hipLaunchKernelGGL(tq_tx_general_kernel<float>, dim3(npan - 1), dim3(256), 0, s, ta);
+			form_v();
 		}
 		FH_HIP(hipGetLastError());
 	}
-	if (fused && npan > 1) { // the V launches on the side stream
+	q.finish_tx(side, tx_on_side);
+	if (npan > 1) { // the V launches on the side stream
 		FH_HIP(hipEventRecord(side.pdone, side.panel));
 		FH_HIP(hipStreamWaitEvent(s, side.pdone, 0));
 	}
-	int *st = ctx().pinned_ints(); // (a pageable target makes the copy a staged, blocking one)
-	FH_HIP(hipMemcpyAsync(st, stat, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-	FH_HIP(hipStreamSynchronize(s));
-#ifdef FH_TQ_TIMING
-	{
-		long long d[32];
-		FH_HIP(hipMemcpy(d, stat + 16, sizeof(d), hipMemcpyDeviceToHost));
-		fprintf(stderr, "tq_panel phases (shader cycles): start %lld: load %lld chol %lld reload %lld lu %lld finish %lld tests %lld out %lld M %lld T %lld\n",
-			d[0], d[1] - d[0], d[2] - d[1], 0LL, d[3] - d[2], d[4] - d[3], d[5] - d[4], d[6] - d[5], d[7] - d[6], d[8] - d[7]);
-		fprintf(stderr, "  load: range %lld loads %lld barrier %lld fill %lld | U, U^-1, V1^-1: %lld | A iterations:", d[12] - d[0], d[13] - d[12], d[14] - d[13], d[1] - d[14], d[15] - d[3]);
-		for (int i = 0; i < 7; ++i)
-			fprintf(stderr, " %lld", d[17 + i] - d[16 + i]);
-		fprintf(stderr, " | B iterations:");
-		for (int i = 0; i < 7; ++i)
-			fprintf(stderr, " %lld", d[25 + i] - d[24 + i]);
-		fprintf(stderr, "\n");
-		double res[3];
-		memcpy(res, d + 9, sizeof(res));
-		fprintf(stderr, "tq_panel residuals of the last panel: |V1 V1^-1 - I| %.3e  |U U^-1 - I| %.3e  |R~ R~^-1 - I| %.3e\n", res[0], res[1], res[2]);
-	}
-#endif
-	*reason = st[0] ? st[2] : TQ_OK;
-	return st[0] ? (idx_t) st[1] : n;
+	return q.columns_done(reason);
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // fp64 driver: the contract of tsqr_factor for double data (columns completed, state of the reference algorithm at that column)
@@ -3189,39 +3122,17 @@ bool tsqr_applicable64(idx_t m, idx_t n, idx_t rs, idx_t cs, idx_t bs, const voi
 	return bs % TQ_PW == 0 || TQ_PW % bs == 0;
 }
 
-template <typename T> static idx_t tsqr_factor_plain(MatV<T> A, MatV<T> H, T *taus, int *reason, idx_t rows_above)
+// the plain schedule: Gram, panel, y, update per panel on one stream
+idx_t tsqr_factor64(MatV<double> A, MatV<double> H, double *taus, int *reason, idx_t rows_above)
 {
-	const idx_t m = A.nrows, n = A.ncols, ld = A.cs, bs = H.nrows;
-	hipStream_t s = ctx().stream;
-	const int npan = (int) ((n + TQ_PW - 1) / TQ_PW);
-	const int ldc = ((int) n + 63) & ~63;
-	const int typ = ldc, ldz = ldc;
-	constexpr int RPV = TqVec<T>::RPV;
-	// (the streaming kernels load 16-byte vectors down the columns without bounds checks: tsqr_applicable64 / tsqr_panel_applicable /
-	// tsqr_factor's schedule 3 admit nothing else)
-	FH_CHECK(A.rs == 1, "tsqr: unit row stride");
+	const TqWork<double> q(A, H, taus, rows_above);
+	const idx_t m = q.m, n = q.n, ld = q.ld;
+	const int npan = q.npan;
+	hipStream_t s = q.s;
+	constexpr int RPV = TqVec<double>::RPV;
 	// 16-byte accesses down the columns where they are aligned (faer's Mat pads the column stride to 64 bytes; a view that starts at an odd
 	// row or has an odd column stride runs the same kernels with scalar accesses)
 	const bool vec = ld % RPV == 0 && (uintptr_t) A.p % 16 == 0;
-	Scratch gp((size_t) TQ_NB * 4096 * 8), cp((size_t) TQ_NB * 64 * TQ_TS * sizeof(T)), sp((size_t) TQ_NB * 256 * sizeof(T));
-	// fp64 workspace: G (NG x 4096), N1, N3, Gf (4096 each), C (NG x 64 x ldc), S (NG x 256), abv (n + 64), Td, Md (npan x 4096 each),
-	//                 Z, B (npan x 64 x ldz each); in the scalar type: Mn (4096), top, A1s (4096 each), Yn (64 x typ); then the status words
-	const size_t nd = (size_t) TQ_NG * 4096 + 3 * 4096 + (size_t) TQ_NG * 64 * ldc + (size_t) TQ_NG * 256 + (size_t) n + 64 + (size_t) 2 * npan * 4096 +
-			  (size_t) 2 * npan * 64 * ldz;
-	Scratch small(nd * 8 + (3 * 4096 + (size_t) 64 * typ) * sizeof(T) + 2048);
-	double *G = small.as<double>();
-	double *N1 = G + (size_t) TQ_NG * 4096, *N3 = N1 + 4096, *Gf = N3 + 4096, *C = Gf + 4096;
-	double *S = C + (size_t) TQ_NG * 64 * ldc, *abv = S + (size_t) TQ_NG * 256;
-	double *Td = abv + n + 64, *Md = Td + (size_t) npan * 4096, *Z = Md + (size_t) npan * 4096, *Bx = Z + (size_t) npan * 64 * ldz;
-	T *Mn = reinterpret_cast<T *>(Bx + (size_t) npan * 64 * ldz), *top = Mn + 4096, *A1s = top + 4096, *Yn = A1s + 4096;
-	int *stat = reinterpret_cast<int *>(Yn + (size_t) 64 * typ);
-	FH_HIP(hipMemsetAsync(stat, 0, 2048, s));
-	FH_HIP(hipMemsetAsync(abv, 0, (size_t) (n + 64) * 8, s));
-	if (rows_above > 0)
-		hipLaunchKernelGGL(tq_above_kernel<T>, dim3((unsigned) n), dim3(256), 0, s, (const T *) A.p, (long) ld, (int) rows_above, abv);
-	const bool cross = bs > TQ_PW && npan > 1;
-	if (cross)
-		FH_HIP(hipMemsetAsync(Z, 0, (size_t) npan * 64 * ldz * 8, s));
 	const int ncu = ctx().stream_cus();
 	// Gram launches of panel [c0, c0 + w), rows from c0 down, against the columns [cx, cx + t) in strips of <= 192
 	auto launch_gram = [&](int c0, int w, int cx, int t, bool first) {
@@ -3229,7 +3140,7 @@ template <typename T> static idx_t tsqr_factor_plain(MatV<T> A, MatV<T> H, T *ta
 		const int nstrip = t == 0 ? 1 : (t + TQ_TS - 1) / TQ_TS;
 		for (int st = 0; st < nstrip; ++st) {
 			const int off = st * TQ_TS;
-			TqGramTArgs<T> g;
+			TqGramTArgs<double> g;
 			g.P = A.p + (long) c0 * ld + c0;
 			g.X = A.p + (long) (cx + off) * ld + c0;
 			g.ld = ld;
@@ -3244,159 +3155,68 @@ template <typename T> static idx_t tsqr_factor_plain(MatV<T> A, MatV<T> H, T *ta
 			g.nchunks = (rows + 8 * RPV * g.nsub - 1) / (8 * RPV * g.nsub);
 			g.want_g = st == 0;
 			g.want_sq = first && st == 0; // (the range guard covers the first strip; tq_range_rest_kernel checks the others)
-			g.Gp = gp.as<double>();
-			g.Cp = cp.as<T>();
-			g.Sp = sp.as<T>();
-			g.stat = stat;
+			g.Gp = q.gp.as<double>();
+			g.Cp = q.cp.as<double>();
+			g.Sp = q.sp.as<double>();
+			g.stat = q.stat;
 			g.c0 = c0;
-			g.A1s = A1s;
+			g.A1s = q.A1s;
 			const int nb = g.nchunks < ncu ? g.nchunks : ncu; // one persistent workgroup per CU (<= TQ_NB partial sums)
 			{
-				ProfScope prof(3, (double) rows * (double) sizeof(T) * ((double) w + (double) g.t));
+				ProfScope prof(3, (double) rows * 8.0 * ((double) w + (double) g.t));
 				switch (g.tp / 32) {
 				case 0: if (vec)
-						hipLaunchKernelGGL((tq_gramT_kernel<T, 0, true>), dim3(nb), dim3(512), 0, s, g);
+						hipLaunchKernelGGL((tq_gramT_kernel<double, 0, true>), dim3(nb), dim3(512), 0, s, g);
 					else
-						hipLaunchKernelGGL((tq_gramT_kernel<T, 0, false>), dim3(nb), dim3(512), 0, s, g); break;
+						hipLaunchKernelGGL((tq_gramT_kernel<double, 0, false>), dim3(nb), dim3(512), 0, s, g); break;
 				case 2: if (vec)
-						hipLaunchKernelGGL((tq_gramT_kernel<T, 2, true>), dim3(nb), dim3(512), 0, s, g);
+						hipLaunchKernelGGL((tq_gramT_kernel<double, 2, true>), dim3(nb), dim3(512), 0, s, g);
 					else
-						hipLaunchKernelGGL((tq_gramT_kernel<T, 2, false>), dim3(nb), dim3(512), 0, s, g); break;
+						hipLaunchKernelGGL((tq_gramT_kernel<double, 2, false>), dim3(nb), dim3(512), 0, s, g); break;
 				case 4: if (vec)
-						hipLaunchKernelGGL((tq_gramT_kernel<T, 4, true>), dim3(nb), dim3(512), 0, s, g);
+						hipLaunchKernelGGL((tq_gramT_kernel<double, 4, true>), dim3(nb), dim3(512), 0, s, g);
 					else
-						hipLaunchKernelGGL((tq_gramT_kernel<T, 4, false>), dim3(nb), dim3(512), 0, s, g); break;
+						hipLaunchKernelGGL((tq_gramT_kernel<double, 4, false>), dim3(nb), dim3(512), 0, s, g); break;
 				default: if (vec)
-						hipLaunchKernelGGL((tq_gramT_kernel<T, 6, true>), dim3(nb), dim3(512), 0, s, g);
+						hipLaunchKernelGGL((tq_gramT_kernel<double, 6, true>), dim3(nb), dim3(512), 0, s, g);
 					else
-						hipLaunchKernelGGL((tq_gramT_kernel<T, 6, false>), dim3(nb), dim3(512), 0, s, g); break;
+						hipLaunchKernelGGL((tq_gramT_kernel<double, 6, false>), dim3(nb), dim3(512), 0, s, g); break;
 				}
 			}
 			const int total = (g.want_g ? 4096 : 0) + 64 * g.tp + (g.want_sq ? 256 : 0);
-			hipLaunchKernelGGL(tq_reduce_kernel<T>, dim3((total + 255) / 256, TQ_NG), dim3(256), 0, s, g.Gp, g.Cp, g.Sp, nb, g.tp, g.want_g, g.want_sq, G, C, ldc,
-					   cx + off - (c0 + w), S, stat, c0, Gf, stat + 128);
+			hipLaunchKernelGGL(tq_reduce_kernel<double>, dim3((total + 255) / 256, TQ_NG), dim3(256), 0, s, g.Gp, g.Cp, g.Sp, nb, g.tp, g.want_g, g.want_sq, q.G, q.C, q.ldc,
+					   cx + off - (c0 + w), q.S, q.stat, c0, q.Gf, q.stat + 128);
 			FH_HIP(hipGetLastError());
 		}
 	};
-	auto launch_panel = [&](int k) {
-		const int c0 = k * TQ_PW;
-		const int w = (int) (n - c0 < TQ_PW ? n - c0 : TQ_PW);
-		const int t = (int) n - c0 - w;
-		TqPanelArgs<T> pa;
-		pa.A = A.p;
-		pa.ld = ld;
-		pa.m = (int) m;
-		pa.r0 = c0;
-		pa.c0 = c0;
-		pa.w = w;
-		pa.n = (int) n;
-		pa.G = Gf;
-		pa.S = S;
-		pa.check_range = k == 0;
-		pa.range_cols = t < TQ_TS ? t : TQ_TS;
-		pa.abv = abv;
-		pa.N1 = N1;
-		pa.N3 = N3;
-		pa.Mn = Mn;
-		pa.top = top;
-		pa.A1s = A1s;
-		pa.Md = Md + (size_t) k * 4096;
-		pa.Td = Td + (size_t) k * 4096;
-		pa.H = H.p;
-		pa.hrs = H.rs;
-		pa.hcs = H.cs;
-		pa.bs = (int) bs;
-		pa.taus = taus;
-		pa.stat = stat;
-		pa.dbg = reinterpret_cast<long long *>(stat + 16);
-		ProfScope prof(4, 1.0);
-		hipLaunchKernelGGL(tq_panel_kernel<T>, dim3(1), dim3(TQ_PT), 0, s, pa);
-	};
-	if (n > TQ_PW + TQ_TS) {
-		hipLaunchKernelGGL(tq_range_rest_kernel<T>, dim3((unsigned) (n - (TQ_PW + TQ_TS))), dim3(256), 0, s, A.p, (long) ld, (int) m, TQ_PW + TQ_TS, stat);
-		FH_HIP(hipGetLastError());
-	}
-	auto tx_args = [&](int stage) {
-		TqTxArgs<T> ta;
-		ta.A = A.p;
-		ta.ld = ld;
-		ta.n = (int) n;
-		ta.bs = (int) bs;
-		ta.Td = Td;
-		ta.Md = Md;
-		ta.Z = Z;
-		ta.ldz = ldz;
-		ta.B = Bx;
-		ta.H = H.p;
-		ta.hrs = H.rs;
-		ta.hcs = H.cs;
-		ta.stat = stat;
-		ta.stage = stage;
-		return ta;
-	};
 	// one block of Q_coeff over all panels (the tall-skinny case): the cross-panel blocks of T in two stages on the side stream -- what
 	// does not need the last panel's kernel beside that panel's Gram launch and kernel, the rest beside the last update (tsqr_factor)
-	const bool two_stage = cross && bs >= n && bs <= (TQ_TX_MAXL + 1) * TQ_PW && npan >= 2;
+	const bool two_stage = q.cross && q.bs >= n && q.bs <= (TQ_TX_MAXL + 1) * TQ_PW && npan >= 2;
 	const TqSide side = tq_side();
 	for (int k = 0; k < npan; ++k) {
 		const int c0 = k * TQ_PW;
-		const int w = (int) (n - c0 < TQ_PW ? n - c0 : TQ_PW);
+		const int w = q.width(k);
 		const int t = (int) n - c0 - w;
-		if (two_stage && k == npan - 1) {
-			FH_HIP(hipEventRecord(side.xfork, s));
-			FH_HIP(hipStreamWaitEvent(side.tx, side.xfork, 0));
-			hipLaunchKernelGGL(tq_tx_kernel<T>, dim3(npan - 1), dim3(256), 0, side.tx, tx_args(1));
-		}
+		if (two_stage && k == npan - 1)
+			q.launch_tx_stage(side, 1);
 		launch_gram(c0, w, c0 + w, t, k == 0);
-		launch_panel(k);
-		if (t > 0) {
-			TqYArgs<T> ya;
-			ya.A = A.p;
-			ya.ld = ld;
-			ya.r0 = c0;
-			ya.cx = c0 + w;
-			ya.w = w;
-			ya.t = t;
-			ya.C = C;
-			ya.ldc = ldc;
-			ya.N1 = N1;
-			ya.N3 = N3;
-			ya.Md = Md + (size_t) k * 4096;
-			ya.abv = abv;
-			ya.Yn = Yn;
-			ya.typ = typ;
-			ya.Z = Z + (size_t) k * 64 * ldz;
-			ya.ldz = ldz;
-			ya.top = top;
-			ya.stat = stat;
-			ya.Sr = S;
-			ya.check_range = k == 0;
-			ya.range_cols = t < TQ_TS ? t : TQ_TS;
-			ya.mrows = (int) m;
-			hipLaunchKernelGGL(tq_y_kernel<T>, dim3((t + 15) / 16), dim3(256), 0, s, ya);
-		} else {
-			hipLaunchKernelGGL(tq_top_kernel<T>, dim3(1), dim3(256), 0, s, A.p, (long) ld, c0, c0, w, (const T *) top, (const int *) stat);
-		}
-		if (two_stage && k == npan - 1) {
-			// stage 2 reads this panel's R block and M: beside the update below (which writes V below that block only)
-			FH_HIP(hipEventRecord(side.xfork, s));
-			FH_HIP(hipStreamWaitEvent(side.tx, side.xfork, 0));
-			hipLaunchKernelGGL(tq_tx_kernel<T>, dim3(npan - 1), dim3(256), 0, side.tx, tx_args(2));
-			FH_HIP(hipEventRecord(side.xdone, side.tx));
-		}
+		q.launch_panel(k);
+		q.launch_y(k, q.S);
+		if (two_stage && k == npan - 1)
+			q.launch_tx_stage(side, 2); // (it reads this panel's R block and M: beside the update below, which writes V below that block only)
 		const int r1 = c0 + w;
 		const int rows = (int) (m - r1);
 		if (rows > 0) {
-			TqUpdTArgs<T> ua;
+			TqUpdTArgs<double> ua;
 			ua.P = A.p + (long) c0 * ld + r1;
 			ua.ld = ld;
 			ua.rows = rows;
 			ua.w = w;
-			ua.Yn = Yn;
-			ua.typ = typ;
-			ua.Mn = Mn;
+			ua.Yn = q.Yn;
+			ua.typ = q.typ;
+			ua.Mn = q.Mn + (size_t) k * 4096;
 			ua.nchunks = (rows + 16 * RPV - 1) / (16 * RPV);
-			ua.stat = stat;
+			ua.stat = q.stat;
 			ua.c0 = c0;
 			const bool v2 = vec && r1 % RPV == 0;
 			const int nwg = ua.nchunks < ncu ? ua.nchunks : ncu; // one persistent 512-thread workgroup per CU
@@ -3411,11 +3231,11 @@ template <typename T> static idx_t tsqr_factor_plain(MatV<T> A, MatV<T> H, T *ta
 				ua.ts = ts;
 				ua.X = A.p + (long) (c0 + w + from) * ld + r1;
 				ua.do_v = last;
-				ProfScope prof(2, (double) rows * (double) sizeof(T) * ((double) w + 2.0 * (double) ts + (last ? (double) w : 0.0)));
+				ProfScope prof(2, (double) rows * 8.0 * ((double) w + 2.0 * (double) ts + (last ? (double) w : 0.0)));
 				if (v2)
-					hipLaunchKernelGGL((tq_updateT_kernel<T, true>), dim3(nwg), dim3(512), 0, s, ua);
+					hipLaunchKernelGGL((tq_updateT_kernel<double, true>), dim3(nwg), dim3(512), 0, s, ua);
 				else
-					hipLaunchKernelGGL((tq_updateT_kernel<T, false>), dim3(nwg), dim3(512), 0, s, ua);
+					hipLaunchKernelGGL((tq_updateT_kernel<double, false>), dim3(nwg), dim3(512), 0, s, ua);
 				from += ts;
 				if (last)
 					break;
@@ -3423,26 +3243,8 @@ template <typename T> static idx_t tsqr_factor_plain(MatV<T> A, MatV<T> H, T *ta
 		}
 		FH_HIP(hipGetLastError());
 	}
-	if (two_stage) {
-		FH_HIP(hipStreamWaitEvent(s, side.xdone, 0));
-	} else if (cross) {
-		if (bs <= (TQ_TX_MAXL + 1) * TQ_PW)
-			hipLaunchKernelGGL(tq_tx_kernel<T>, dim3(npan - 1), dim3(256), 0, s, tx_args(0));
-		else
-			hipLaunchKernelGGL(tq_tx_general_kernel<T>, dim3(npan - 1), dim3(256), 0, s, tx_args(0));
-		FH_HIP(hipGetLastError());
-	}
-	int *st = ctx().pinned_ints();
-	FH_HIP(hipMemcpyAsync(st, stat, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-	FH_HIP(hipStreamSynchronize(s));
-	*reason = st[0] ? st[2] : TQ_OK;
-	return st[0] ? (idx_t) st[1] : n;
-}
-
-
-idx_t tsqr_factor64(MatV<double> A, MatV<double> H, double *taus, int *reason, idx_t rows_above)
-{
-	return tsqr_factor_plain<double>(A, H, taus, reason, rows_above);
+	q.finish_tx(side, two_stage);
+	return q.columns_done(reason);
 }
 
 } // namespace fh

@@ -482,10 +482,6 @@ FAER_HIP_API int faer_hip_debug_lu_leaf_width(size_t nrows, FaerHipDType dtype, 
 /* tests: run every leaf of the partial-pivot LU on the non-cooperative path (the fallback for panels taller than the
  * cooperative kernel can keep resident and for the rerun after an exchange timeout) */
 FAER_HIP_API void faer_hip_debug_lu_force_general(int on);
-/* tests / A-B measurements: 1 = the look-ahead LU and Cholesky drivers lend the panel stream's idle compute units to their big
- * trailing products (helper launches that pull tiles from per-XCD counters).  Default 0: measured without gain on MI355X
- * (profiles/r06_exp_lend.txt); the factors do not depend on it. */
-FAER_HIP_API void faer_hip_debug_lend_cus(int on);
 /* tests: switch-over points of the look-ahead LU driver, in rows below the panel (0 = the tuned default): 256-column staged steps
  * below `nb2_from`, pipelined bulk-bound steps from `pipe_from` on, look-ahead at all from `la_min_cols` columns.  Lets a test drive
  * every phase of the driver and the transitions between them at N = 2-6 k; pivots and factors do not depend on the plan. */
@@ -494,12 +490,9 @@ FAER_HIP_API void faer_hip_debug_lu_plan(size_t nb2_from, size_t pipe_from, size
  * qr_factor_in_place (== ncols: the whole factorization; fewer: a panel was rejected and the classic path finished; -1: the
  * path was not applicable) */
 FAER_HIP_API long faer_hip_debug_qr_one_pass_columns(void);
-/* tests / A-B measurements: 0 = the one-pass QR path applies a panel and forms the next panel's Gram products in separate launches (the
- * round 3-5 schedule), 1 (default) = in one pass per panel with the next panel's kernel beside its second half (csrc/tsqr.hip), 2 = the
- * same without the raw copy of the panel (what matrices of more than 4.19 M rows run: V = P M as a launch of its own behind U2), 3 = the
- * plain schedule (Gram, panel, y, update per panel) on the streaming kernels of the fp64 instantiation, for fp32 data with 16-byte aligned
- * columns (5e5 x 256: 1.80 ms against 1.68 fused -- its panel kernels are not hidden; ahead of the fused schedule below ~50000 rows). */
-FAER_HIP_API void faer_hip_debug_qr_fused(int on);
+/* tests: 1 (default) = the fp32 one-pass QR path (csrc/tsqr.hip) keeps a raw copy of the panel for the launches that read it after V has
+ * overwritten it, where the copy fits in 1 GiB; 0 = never (what matrices of more than 4.19 M rows run: V = P M as a launch of its own). */
+FAER_HIP_API void faer_hip_debug_qr_panel_copy(int on);
 /* tests / A-B measurements: 0 = fp64 matrices never take the one-pass tall-skinny QR path (the classic path of rounds 1-6 runs), 1 (default) =
  * they take it under the same shape rule as fp32 (rows >= 1024, rows >= 3 cols, cols <= 512, unit row stride; columns that are not 16-byte aligned run scalar-access variants of the kernels). */
 FAER_HIP_API void faer_hip_debug_qr_one_pass_f64(int on);
