@@ -105,6 +105,23 @@ class LltRegularization(C.Structure):
     _fields_ = [("dynamic_regularization_delta", C.c_void_p), ("dynamic_regularization_epsilon", C.c_void_p)]
 
 
+class TridiagParams(C.Structure):
+    _fields_ = [("par_threshold", C.c_size_t)]
+
+
+class SelfAdjointEvdParams(C.Structure):
+    """include/faer_hip.h FaerSelfAdjointEvdParams {tridiag: {par_threshold}, recursion_threshold}"""
+    _fields_ = [("tridiag", TridiagParams), ("recursion_threshold", C.c_size_t)]
+
+
+class EvdStatus(C.Structure):
+    """include/faer_hip.h FaerEvdStatus: tag (0 Ok, 1 NoConvergence), then a union of one size_t"""
+    _fields_ = [("tag", C.c_int), ("padding", C.c_size_t)]
+
+
+EVD_OK, EVD_NO_CONVERGENCE = 0, 1
+
+
 BCAST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
 
 
@@ -426,6 +443,29 @@ def tridiag_in_place(a, householder):
     fn.restype = None
     fn(_mat(a, MatMut), _mat(householder, MatMut))
     return a, householder
+
+
+def self_adjoint_evd(a, s, u=None, params=None, par=PAR_SEQ):
+    """faer::linalg::evd::self_adjoint_evd (evd/mod.rs:270): eigenvalues of the self-adjoint `a` (n x n, only its lower
+    triangle is read, never written) in ascending order into the 1-D `s`; with `u` (n x n) the orthonormal eigenvectors,
+    column j going with s[j].  Returns the status tag (EVD_OK or EVD_NO_CONVERGENCE)."""
+    suf, _, _ = _dtype_suffix(a)
+    L = lib()
+    if params is None:
+        pf = getattr(L, f"libfaer_v0_23_SelfAdjointEvdParams_{suf}")
+        pf.restype = SelfAdjointEvdParams
+        params = pf()
+    if _is_torch(s):
+        assert s.dim() == 1
+        sv = VecRef(s.data_ptr(), s.shape[0], s.stride(0))
+    else:
+        assert s.ndim == 1
+        sv = VecRef(s.ctypes.data, s.shape[0], s.strides[0] // s.itemsize)
+    um = _mat(u, MatMut) if u is not None else MatMut(None, a.shape[0], 0, 1, a.shape[0])
+    fn = getattr(L, f"libfaer_v0_23_self_adjoint_evd_{suf}")
+    fn.restype = EvdStatus
+    st = fn(_mat(a), um, sv, par, MemAlloc(None, 0), params)
+    return st.tag
 
 
 def hessenberg_in_place(a, householder):

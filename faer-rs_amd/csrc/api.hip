@@ -670,6 +670,35 @@ void colpiv_qr_inverse_api(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMat
 	permute_rows_dev_api<T, I>(o.dev, static_cast<const I *>(pb.ptr)); // permute_rows_in_place(out, col_perm.inverse())
 }
 
+// evd/mod.rs:270-425 behind lib.rs:2385-2399 (U.ncols == 0: no eigenvectors)
+template <typename T> FaerEvdStatus self_adjoint_evd_api(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerSelfAdjointEvdParams params)
+{
+	const size_t n = A.nrows;
+	FH_CHECK(A.ncols == n && S.len == n, "self_adjoint_evd: A must be square and S must have n entries"); // mod.rs:279
+	FH_CHECK(U.ncols == 0 || (U.nrows == n && U.ncols == n), "self_adjoint_evd: U must be n x n (or have no columns)");
+	FaerEvdStatus st;
+	memset(&st, 0, sizeof(st));
+	st.tag = FaerEvdStatus_Ok;
+	if (n == 0)
+		return st;
+	int r;
+	{
+		Staged<const T> a(view<T>(A), true, false);
+		FaerMatMut Sm{S.ptr, S.len, 1, S.stride, 0};
+		Staged<T> s(view<T>(Sm), false, true);
+		const idx_t leaf = evd_leaf_size(params.recursion_threshold), bs = (idx_t) qr_block_size(n, n);
+		if (U.ncols == 0) {
+			r = self_adjoint_evd_dev<T>(a.dev, MatV<T>{nullptr, (idx_t) n, (idx_t) n, 1, (idx_t) n}, s.dev.p, s.dev.rs, leaf, bs);
+		} else {
+			Staged<T> u(view<T>(U), false, true);
+			r = self_adjoint_evd_dev<T>(a.dev, u.dev, s.dev.p, s.dev.rs, leaf, bs);
+		}
+	}
+	if (r != 0)
+		st.tag = FaerEvdStatus_NoConvergence;
+	return st;
+}
+
 } // namespace
 
 extern "C" {
@@ -1397,6 +1426,30 @@ void faer_hip_debug_dump_timing(void)
 	lu_dump_timing();
 	gemm_dump_timing();
 }
+
+#define X(suf, T)                                                                                                      \
+	FaerTridiagParams libfaer_v0_23_TridiagParams_##suf(void) { return FaerTridiagParams{192 * 256}; }              \
+	FaerSelfAdjointEvdParams libfaer_v0_23_SelfAdjointEvdParams_##suf(void)                                        \
+	{                                                                                                              \
+		return FaerSelfAdjointEvdParams{FaerTridiagParams{192 * 256}, 128};                                    \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_self_adjoint_evd_scratch_##suf(size_t dim, FaerComputeEigenvectors compute_U, FaerPar par, \
+								  FaerSelfAdjointEvdParams params)                          \
+	{                                                                                                              \
+		(void) compute_U;                                                                                      \
+		(void) par;                                                                                            \
+		(void) params;                                                                                         \
+		return layout((2 * dim * dim + 12 * dim) * sizeof(T), 64);                                             \
+	}                                                                                                              \
+	FaerEvdStatus libfaer_v0_23_self_adjoint_evd_##suf(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerPar par,      \
+							   FaerMemAlloc mem, FaerSelfAdjointEvdParams params)               \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) mem;                                                                                            \
+		return self_adjoint_evd_api<T>(A, U, S, params);                                                       \
+	}
+FH_FOR_DTYPES(X)
+#undef X
 
 void faer_hip_tridiag_in_place_f64(FaerMatMut A, FaerMatMut householder) { tridiag_api<double>(A, householder); }
 void faer_hip_tridiag_in_place_f32(FaerMatMut A, FaerMatMut householder) { tridiag_api<float>(A, householder); }

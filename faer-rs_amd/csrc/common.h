@@ -409,6 +409,13 @@ template <typename T> void hessenberg_dev(MatV<T> A, MatV<T> H);
 template <typename T>
 void apply_householder_sequence_left_dev(MatV<const T> V, MatV<const T> H, MatV<T> M, bool transpose);
 
+// evd/mod.rs:270 self_adjoint_evd (evd.hip): S (n entries, stride ss, device) <- ascending eigenvalues of the self-adjoint A
+// (lower triangle read), U (n x n, device) <- eigenvectors unless U.p == nullptr.  Leaves of the divide and conquer have at
+// most `leaf` rows (evd_leaf_size), `bs` is the block size of the tridiagonalization's Householder factors.  Returns 0, or 1
+// for NoConvergence (a non-finite tridiagonal or a leaf over its iteration cap).
+idx_t evd_leaf_size(size_t recursion_threshold);
+template <typename T> int self_adjoint_evd_dev(MatV<const T> A, MatV<T> U, T *S, idx_t ss, idx_t leaf, idx_t bs);
+
 // small utility kernels (util.hip)
 template <typename T> void fill_dev(MatV<T> A, DstKind kind, T value);
 template <typename T> void copy_dev(MatV<T> dst, MatV<const T> src);

@@ -1,0 +1,1150 @@
+// Self-adjoint eigendecomposition -- faer/src/linalg/evd/mod.rs:270-425 (self_adjoint_evd) with the divide and
+// conquer solver of the symmetric tridiagonal problem, evd/tridiag_evd.rs:270-660, on the device.
+//
+//   copy lower(A) -> tridiag_dev (qr.hip) -> diag / offdiag -> tridiagonal solve -> block Householder back-transform
+//   (apply_householder_sequence_left_dev) -> S.
+//
+// The tridiagonal solve follows the reference's recursion (split at n / 2, rank-one tear d[n1-1] -= |rho|, d[n1] -= |rho|)
+// but runs it level by level, bottom up; every launch covers all nodes of one level:
+//   * evd_leaf_kernel: implicit symmetric QR with the Wilkinson shift (tridiag_evd.rs:9-190) on every leaf of at most
+//     min(max(recursion_threshold, 4), 64) rows (evd_leaf_size; the kernel holds up to 128), one single-wave workgroup per
+//     leaf, the leaf's eigenvector block in LDS (128 x 129 fp64 = 129 KiB at most).  Lane 0 generates a sweep's Givens rotations; then every lane applies the whole sweep
+//     to its rows of U (rotations on the right act on each row on its own: one barrier per sweep).
+//   * evd_merge_prep_kernel (one workgroup per merge): z from the last row of U0 and the first row of U1, the merge of
+//     the two ascending halves (pl_before), deflation of small rho z_i and of runs of nearly equal d (Householder
+//     reflector as the reference), compaction of the k non-deflated entries (:370-480).
+//   * evd_secular_kernel (one wavefront per root): the reference's secular_eq_root_finder (svd/bidiag_svd.rs:7); a root
+//     is kept as (pole, mu) so that lambda_j - d_i = (d_i - pole_j) - mu_j never cancels.
+//   * evd_loewner_kernel (one thread per entry): Gu-Eisenstat z-hat recomputed from the roots, and the ascending order of
+//     the merged eigenvalues (pr).
+//   * evd_qhat_kernel (one workgroup per column): the reference's repaired_u in the final column order, deflated columns
+//     as unit vectors, the run reflectors applied, rows mapped back through pl_before.
+//   * two MFMA products per merge on gemm_dev: U[0:n1, :] = U0 Qhat_top, U[n1:, :] = U1 Qhat_bot (:595-598).
+// The shapes of every launch follow from n alone (deflation only changes the contents of Qhat), so the solve has no
+// host synchronization; the call reads back one status word at its end.
+#include <cmath>
+
+#include "common.h"
+
+namespace fh {
+
+namespace {
+
+template <typename T> struct EvdTraits;
+template <> struct EvdTraits<double> {
+	static constexpr double eps = 2.220446049250313e-16;
+	static constexpr double sml = 2.2250738585072014e-308;
+	static constexpr long iter_factor = 32; // max(30, nbits / 2)
+};
+template <> struct EvdTraits<float> {
+	static constexpr float eps = 1.1920929e-07f;
+	static constexpr float sml = 1.17549435e-38f;
+	static constexpr long iter_factor = 30;
+};
+
+__device__ __forceinline__ double ev_abs(double x) { return fabs(x); }
+__device__ __forceinline__ float ev_abs(float x) { return fabsf(x); }
+__device__ __forceinline__ double ev_sqrt(double x) { return sqrt(x); }
+__device__ __forceinline__ float ev_sqrt(float x) { return sqrtf(x); }
+__device__ __forceinline__ double ev_hypot(double x, double y) { return hypot(x, y); }
+__device__ __forceinline__ float ev_hypot(float x, float y) { return hypotf(x, y); }
+template <typename T> __device__ __forceinline__ T ev_max(T a, T b) { return a > b ? a : b; } // fmax of two non-NaN values
+template <typename T> __device__ __forceinline__ T ev_inf() { return (T) INFINITY; }
+
+template <typename T> __device__ __forceinline__ T wave_sum(T v)
+{
+	for (int o = 32; o > 0; o >>= 1)
+		v += __shfl_xor(v, o);
+	return __shfl(v, 0); // every lane takes lane 0's sum: the callers branch on it, so all lanes must see the same bits
+}
+template <typename T> __device__ __forceinline__ T wave_max(T v)
+{
+	for (int o = 32; o > 0; o >>= 1)
+		v = ev_max(v, __shfl_xor(v, o));
+	return v;
+}
+// 256-thread blocks: sum / max of one value per thread, the result in every thread
+template <typename T, bool MAX> __device__ T block_reduce(T v, T *red)
+{
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	v = MAX ? wave_max(v) : wave_sum(v);
+	__syncthreads(); // red may still be read by the previous reduction
+	if (lane == 0)
+		red[w] = v;
+	__syncthreads();
+	T r = red[0];
+	for (int i = 1; i < 4; ++i)
+		r = MAX ? ev_max(r, red[i]) : r + red[i];
+	return r;
+}
+
+// per-level work vectors (n entries each, a merge at offset `off` owns [off, off + its size)); per-merge scalars by the
+// merge's index in its level
+template <typename T> struct EvdWork {
+	T *z, *pd0, *pz0, *pd, *pz, *hh, *mu, *sh, *zh;
+	int *plb, *pla, *rl, *pr;
+	int *k, *applied;
+	T *rho;
+};
+
+// ---- input --------------------------------------------------------------------------------------
+template <typename T> struct EvdBits;
+template <> struct EvdBits<double> {
+	typedef unsigned long long U;
+	static __device__ U of(double x) { return (U) __double_as_longlong(x); }
+	static __device__ double val(U u) { return __longlong_as_double((long long) u); }
+	static constexpr double rmin = 1.0010415475915505e-146, rmax = 9.989595361011175e+145; // sqrt(sml / eps), 1 / rmin
+};
+template <> struct EvdBits<float> {
+	typedef unsigned int U;
+	static __device__ U of(float x) { return __float_as_uint(x); }
+	static __device__ float val(U u) { return __uint_as_float(u); }
+	static constexpr float rmin = 3.1401849e-16f, rmax = 3.1845258e+15f;
+};
+
+// trid <- lower(A) (mod.rs:327 copy_from_triangular_lower), zero above the diagonal: the strict upper triangle of A is never
+// read.  Also max |lower(A)| (the bits of a non-negative float order like unsigned integers): one atomic per block.
+template <typename T> __global__ __launch_bounds__(256) void evd_copy_lower_kernel(const T *A, idx_t rs, idx_t cs, T *X, idx_t n,
+										   typename EvdBits<T>::U *amax)
+{
+	__shared__ T red[4];
+	const idx_t t = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
+	T v = 0;
+	if (t < n * n) {
+		const idx_t i = t % n, j = t / n;
+		v = i >= j ? A[i * rs + j * cs] : (T) 0;
+		X[t] = v;
+	}
+	const T m = block_reduce<T, true>(ev_abs(v), red);
+	if (threadIdx.x == 0)
+		atomicMax(amax, EvdBits<T>::of(m));
+}
+
+// the scaling of LAPACK's xSYEV: a matrix whose largest entry lies outside [rmin, rmax] is scaled by a power of two into that
+// range (exact), the eigenvalues are scaled back at the end; fac[0] <- the factor (1 inside the range)
+template <typename T> __global__ void evd_scale_kernel(T *X, idx_t nn, const typename EvdBits<T>::U *amax, T *fac)
+{
+	const T a = EvdBits<T>::val(*amax);
+	int e = 0;
+	if (isfinite(a) && a > (T) 0) {
+		if (a > EvdBits<T>::rmax)
+			e = ilogb((double) EvdBits<T>::rmax) - ilogb((double) a) - 1;
+		else if (a < EvdBits<T>::rmin)
+			e = ilogb((double) EvdBits<T>::rmin) - ilogb((double) a) + 1;
+	}
+	if (e == 0) {
+		if (blockIdx.x == 0 && threadIdx.x == 0)
+			fac[0] = 1;
+		return;
+	}
+	const T f = (T) ldexp(1.0, e);
+	const idx_t t = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (t < nn)
+		X[t] *= f;
+	if (t == 0)
+		fac[0] = f;
+}
+
+// diag / offdiag of the tridiagonal T (mod.rs:345-356) and max(|d|, |e|); any non-finite entry sets the status before any iteration
+template <typename T>
+__global__ __launch_bounds__(256) void evd_extract_kernel(const T *X, idx_t n, T *D, T *E, typename EvdBits<T>::U *tmax, int *status)
+{
+	__shared__ T red[4];
+	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
+	T m = 0;
+	if (i < n) {
+		const T d = X[i + i * n];
+		const T e = i + 1 < n ? X[i + 1 + i * n] : (T) 0;
+		D[i] = d;
+		E[i] = e;
+		if (!isfinite(d) || !isfinite(e))
+			status[0] = 1;
+		m = ev_max(ev_abs(d), ev_abs(e));
+	}
+	m = block_reduce<T, true>(m, red);
+	if (threadIdx.x == 0)
+		atomicMax(tmax, EvdBits<T>::of(m));
+}
+
+// The root finder's stopping tests compare secular-function values with eps in absolute terms (bidiag_svd.rs:64-66), so
+// the solve is not scale invariant: the tridiagonal is scaled by a power of two (exact) to max(|d|, |e|) in [1, 2).
+// tfac[0] <- the factor.
+template <typename T> __global__ void evd_tscale_kernel(T *D, T *E, idx_t n, const typename EvdBits<T>::U *tmax, T *tfac)
+{
+	const T a = EvdBits<T>::val(*tmax);
+	const int e = isfinite(a) && a > (T) 0 ? -ilogb((double) a) : 0;
+	const T f = (T) ldexp(1.0, e);
+	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) {
+		D[i] *= f;
+		E[i] *= f;
+	}
+	if (i == 0)
+		tfac[0] = f;
+}
+
+// rank-one tears of every merge (tridiag_evd.rs:290-296).  With leaves of at least 4 rows no two merges touch the same entry.
+template <typename T> __global__ void evd_tear_kernel(const int *merges, int count, T *D, const T *E, const int *status)
+{
+	const int t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= count || status[0])
+		return;
+	const idx_t off = merges[3 * t], n1 = merges[3 * t + 2];
+	const T r = ev_abs(E[off + n1 - 1]);
+	D[off + n1 - 1] -= r;
+	D[off + n1] -= r;
+}
+
+// ---- leaves: QR algorithm -----------------------------------------------------------------------
+constexpr int EVD_LEAF_MAX = 128;
+
+template <typename T> __device__ __forceinline__ void make_givens(T p, T q, T &c, T &s)
+{
+	// linalg/jacobi.rs:16-55
+	if (q == (T) 0) {
+		c = p < (T) 0 ? (T) -1 : (T) 1;
+		s = 0;
+	} else if (p == (T) 0) {
+		c = 0;
+		s = q < (T) 0 ? (T) 1 : (T) -1;
+	} else if (ev_abs(p) > ev_abs(q)) {
+		const T t = q / p;
+		T u = ev_hypot(t, (T) 1);
+		if (p < (T) 0)
+			u = -u;
+		c = (T) 1 / u;
+		s = -t * c;
+	} else {
+		const T t = p / q;
+		T u = ev_hypot(t, (T) 1);
+		if (q < (T) 0)
+			u = -u;
+		s = -(T) 1 / u;
+		c = -t * s;
+	}
+}
+
+// highest index < lim whose bit is set in the 128-bit mask (lo: indices 0..63, hi: 64..127), -1 if none
+__device__ __forceinline__ int highest_below(unsigned long long lo, unsigned long long hi, int lim)
+{
+	if (lim > 64) {
+		const unsigned long long h = lim >= 128 ? hi : hi & ((1ull << (lim - 64)) - 1ull);
+		if (h)
+			return 127 - __clzll((long long) h);
+		lim = 64;
+	}
+	if (lim <= 0)
+		return -1;
+	const unsigned long long l = lim >= 64 ? lo : lo & ((1ull << lim) - 1ull);
+	return l ? 63 - __clzll((long long) l) : -1;
+}
+
+template <typename T> constexpr size_t evd_leaf_lds(int m) { return ((size_t) m * (m + 1) + 4 * EVD_LEAF_MAX) * sizeof(T) + EVD_LEAF_MAX * sizeof(int); }
+
+// one wavefront per leaf; leaves[3 * b ..]: offset, rows, destination buffer (0: U0, 1: U1)
+template <typename T>
+__global__ __launch_bounds__(64) void evd_leaf_kernel(const int *leaves, T *D, const T *E, T *U0, idx_t rs0, idx_t cs0, T *U1, idx_t rs1,
+						      idx_t cs1, int *status)
+{
+	extern __shared__ __align__(16) unsigned char evd_lds[];
+	const int tid = threadIdx.x;
+	const idx_t off = leaves[3 * blockIdx.x];
+	const int m = leaves[3 * blockIdx.x + 1];
+	T *Ug = leaves[3 * blockIdx.x + 2] ? U1 : U0;
+	const idx_t rs = leaves[3 * blockIdx.x + 2] ? rs1 : rs0, cs = leaves[3 * blockIdx.x + 2] ? cs1 : cs0;
+	if (status[0])
+		return;
+	const int ld = m + 1;
+	T *u = reinterpret_cast<T *>(evd_lds); // row major, u[i * ld + j] = U(i, j): lane i owns rows i and i + 64
+	T *d = u + (size_t) m * ld, *e = d + EVD_LEAF_MAX, *rc = e + EVD_LEAF_MAX, *rsn = rc + EVD_LEAF_MAX;
+	int *perm = reinterpret_cast<int *>(rsn + EVD_LEAF_MAX);
+	__shared__ int sh_kend;
+	const T eps = EvdTraits<T>::eps, sml = EvdTraits<T>::sml;
+
+	for (int t = tid; t < m * ld; t += 64)
+		u[t] = (t % ld) == (t / ld) ? (T) 1 : (T) 0;
+	for (int i = tid; i < m; i += 64) {
+		d[i] = D[off + i];
+		e[i] = i + 1 < m ? E[off + i] : (T) 0;
+		perm[i] = i;
+	}
+	__syncthreads();
+	T scale = 1;
+	bool fail = false;
+	if (m == 2) {
+		// tridiag_evd.rs:27-82
+		if (tid == 0) {
+			const T a = d[0], dd = d[1], b = e[0], half = (T) 0.5;
+			const T t0 = ev_hypot(a - dd, b * (T) 2) * half, t1 = (a + dd) * half;
+			const T r0 = t1 - t0, r1 = t1 + t0;
+			const T tol = ev_max(ev_abs(r0), ev_abs(r1)) * eps;
+			T u00 = 1, u10 = 0, u01 = 0, u11 = 1;
+			if (r1 - r0 <= tol) {
+			} else if (ev_abs(b) <= tol) {
+				if (!(d[0] < d[1])) {
+					u00 = 0;
+					u10 = 1;
+					u01 = 1;
+					u11 = 0;
+				}
+			} else {
+				const T tau = ((dd - a) / b) * half;
+				T t = (T) 1 / (ev_abs(tau) + ev_hypot(tau, (T) 1));
+				if (tau < (T) 0)
+					t = -t;
+				T c = ev_hypot(t, (T) 1);
+				T s = c * t;
+				const T r = ev_hypot(c, s);
+				c = c / r;
+				s = s / r;
+				const T r0_r = (c * a - s * b) / c;
+				if (ev_abs(r0 - r0_r) < r1 - r0_r) {
+					u00 = c;
+					u10 = -s;
+					u01 = s;
+					u11 = c;
+				} else {
+					u01 = c;
+					u11 = -s;
+					u00 = s;
+					u10 = c;
+				}
+			}
+			u[0] = u00;
+			u[1] = u01;
+			u[ld] = u10;
+			u[ld + 1] = u11;
+			d[0] = r0;
+			d[1] = r1;
+		}
+		__syncthreads();
+	} else if (m > 2) {
+		// tridiag_evd.rs:84-190
+		T mx = 0;
+		for (int i = tid; i < m; i += 64)
+			mx = ev_max(mx, ev_max(ev_abs(d[i]), ev_abs(e[i])));
+		mx = wave_max(mx);
+		if (mx != (T) 0) {
+			scale = mx;
+			const T inv = (T) 1 / mx;
+			for (int i = tid; i < m; i += 64) {
+				d[i] *= inv;
+				e[i] *= inv;
+			}
+			__syncthreads();
+			int start = 0, end = m - 1;
+			const long max_iters = EvdTraits<T>::iter_factor * (long) m * (long) m;
+			for (long iter = 0; iter < max_iters; ++iter) {
+				for (int i = start + tid; i < end; i += 64) {
+					const T ei = ev_abs(e[i]);
+					if (ei < sml || ei < eps * ev_hypot(d[i], d[i + 1]))
+						e[i] = 0;
+				}
+				__syncthreads();
+				const bool v0 = tid < m - 1, v1 = tid + 64 < m - 1;
+				const T e0 = v0 ? e[tid] : (T) 0, e1 = v1 ? e[tid + 64] : (T) 0;
+				const unsigned long long nz0 = __ballot(v0 && e0 != (T) 0), nz1 = __ballot(v1 && e1 != (T) 0);
+				const unsigned long long z0 = __ballot(v0 && e0 == (T) 0), z1 = __ballot(v1 && e1 == (T) 0);
+				end = highest_below(nz0, nz1, end) + 1; // while end > 0 && offdiag[end - 1] == 0: end -= 1
+				if (end == 0)
+					break;
+				if (iter + 1 == max_iters) {
+					fail = true;
+					break;
+				}
+				start = highest_below(z0, z1, end - 1) + 1; // while start > 0 && offdiag[start - 1] != 0: start -= 1
+				if (tid == 0) {
+					const T td = (d[end - 1] - d[end]) * (T) 0.5;
+					const T ee = e[end - 1];
+					T mu = d[end];
+					if (td == (T) 0) {
+						mu -= ev_abs(ee);
+					} else if (ee != (T) 0) {
+						const T e2 = ee * ee;
+						T h = ev_hypot(td, ee);
+						if (!(td > (T) 0))
+							h = -h;
+						if (e2 == (T) 0)
+							mu = mu - ee / ((td + h) / ee);
+						else
+							mu = mu - e2 / (td + h);
+					}
+					T x = d[start] - mu, z = e[start];
+					int k = start;
+					T dk = d[k], ek = e[k];
+					while (k < end && z != (T) 0) {
+						T c, s;
+						make_givens(x, z, c, s);
+						const T dk1 = d[k + 1];
+						const T sdk = s * dk + c * ek;
+						const T dkp1 = s * ek + c * dk1;
+						d[k] = c * (c * dk - s * ek) - s * (c * ek - s * dk1);
+						const T nd1 = s * sdk + c * dkp1;
+						const T nek = c * sdk - s * dkp1;
+						d[k + 1] = nd1;
+						e[k] = nek;
+						if (k > start)
+							e[k - 1] = c * e[k - 1] - s * z;
+						x = nek;
+						T ek1 = e[k + 1];
+						if (k < end - 1) {
+							z = -s * ek1;
+							ek1 = c * ek1;
+							e[k + 1] = ek1;
+						}
+						rc[k] = c;
+						rsn[k] = s;
+						dk = nd1;
+						ek = ek1;
+						++k;
+					}
+					sh_kend = k;
+				}
+				__syncthreads();
+				const int kend = sh_kend;
+				for (int i = tid; i < m; i += 64) {
+					// apply_on_the_right_in_place on columns (k + 1, k): U(:, k+1) = c a + s b, U(:, k) = c b - s a
+					T *row = u + (size_t) i * ld;
+					T x = row[start];
+					for (int k = start; k < kend; ++k) {
+						const T a = row[k + 1], c = rc[k], s = rsn[k];
+						row[k] = c * x - s * a;
+						x = c * a + s * x;
+					}
+					row[kend] = x;
+				}
+				__syncthreads();
+			}
+			if (!fail && tid == 0) {
+				// selection sort with column swaps (:170-186)
+				for (int i = 0; i < m - 1; ++i) {
+					int idx = i;
+					T mn = d[i];
+					for (int k = i + 1; k < m; ++k)
+						if (d[k] < mn) {
+							idx = k;
+							mn = d[k];
+						}
+					if (idx != i) {
+						const T a = d[i];
+						d[i] = d[idx];
+						d[idx] = a;
+						const int p = perm[i];
+						perm[i] = perm[idx];
+						perm[idx] = p;
+					}
+				}
+			}
+			__syncthreads();
+		}
+	}
+	if (fail) {
+		if (tid == 0)
+			status[0] = 1;
+		return;
+	}
+	for (int i = tid; i < m; i += 64)
+		D[off + i] = d[i] * scale;
+	for (int t = tid; t < m * m; t += 64) {
+		const int i = t % m, j = t / m;
+		Ug[(off + i) * rs + (off + j) * cs] = u[(size_t) i * ld + perm[j]];
+	}
+}
+
+// ---- merges ---------------------------------------------------------------------------------------
+// merges[3 * b ..]: offset, size n, n1 (the first half)
+template <typename T>
+__global__ __launch_bounds__(256) void evd_merge_prep_kernel(const int *merges, const T *D, const T *E, const T *Uc, idx_t rs, idx_t cs,
+							     EvdWork<T> w, const int *status)
+{
+	__shared__ T red[4];
+	__shared__ int applied_sh;
+	__shared__ int scan[257];
+	if (status[0])
+		return;
+	const int b = blockIdx.x, tid = threadIdx.x;
+	const idx_t off = merges[3 * b];
+	const int n = merges[3 * b + 1], n1 = merges[3 * b + 2], n2 = n - n1;
+	const T eps = EvdTraits<T>::eps, sml = EvdTraits<T>::sml;
+	const T rho_in = E[off + n1 - 1];
+	const bool neg = rho_in < (T) 0;
+	const T inv_sqrt2 = ev_sqrt((T) 0.5);
+	const T *d = D + off;
+	T *z = w.z + off, *pd0 = w.pd0 + off, *pz0 = w.pz0 + off;
+	int *plb = w.plb + off, *rl = w.rl + off;
+	if (tid == 0)
+		applied_sh = 0;
+	// z (tridiag_evd.rs:370-380) and pl_before (:382-397): the merge position of an entry of either ascending half is its
+	// index plus the entries of the other half that precede it (a tie takes the second half first)
+	for (int i = tid; i < n; i += 256) {
+		T uv;
+		int pos;
+		if (i < n1) {
+			uv = Uc[(off + n1 - 1) * rs + (off + i) * cs];
+			const T x = d[i];
+			int lo = 0, hi = n2; // count of d1[j] <= x
+			while (lo < hi) {
+				const int mid = (lo + hi) >> 1;
+				if (d[n1 + mid] <= x)
+					lo = mid + 1;
+				else
+					hi = mid;
+			}
+			pos = i + lo;
+		} else {
+			uv = Uc[(off + n1) * rs + (off + i) * cs];
+			if (neg)
+				uv = -uv;
+			const T x = d[i];
+			int lo = 0, hi = n1; // count of d0[p] < x
+			while (lo < hi) {
+				const int mid = (lo + hi) >> 1;
+				if (d[mid] < x)
+					lo = mid + 1;
+				else
+					hi = mid;
+			}
+			pos = (i - n1) + lo;
+		}
+		z[i] = uv * inv_sqrt2;
+		plb[pos] = i;
+	}
+	__syncthreads();
+	const T rho = ev_abs(rho_in) * (T) 2;
+	T dm = 0, zm = 0;
+	for (int i = tid; i < n; i += 256) {
+		const int p = plb[i];
+		const T dv = d[p], zv = z[p];
+		pd0[i] = dv;
+		pz0[i] = zv;
+		dm = ev_max(dm, ev_abs(dv));
+		zm = ev_max(zm, ev_abs(zv));
+	}
+	const T dmax = block_reduce<T, true>(dm, red);
+	const T zmax = block_reduce<T, true>(zm, red);
+	const T tol = (T) 8 * eps * ev_max(dmax, zmax);
+	const bool all_deflated = rho * zmax <= tol; // :404-418
+	if (!all_deflated) {
+		for (int i = tid; i < n; i += 256) {
+			if (ev_abs(rho * pz0[i]) <= tol)
+				pz0[i] = 0;
+			// a gap above tol always starts a run (the entries are ascending): mark the segments that the walkers below own
+			rl[i] = (i == 0 || pd0[i] - pd0[i - 1] > tol) ? -1 : 0;
+		}
+		__syncthreads();
+		// runs of nearly equal d (:424-452), one walker per segment.  A run is measured from its first entry, so a segment may
+		// hold several runs: a walker starts only at a segment mark (-1), which no other thread overwrites (the walkers write
+		// run lengths >= 1 at run starts and 0 inside runs; the next segment's mark stays nonzero and stops the walk)
+		for (int i = tid; i < n; i += 256) {
+			if (rl[i] != -1)
+				continue;
+			int idx = i;
+			while (true) {
+				int run_len = 1;
+				const T d_prev = pd0[idx];
+				while (idx + run_len < n && pd0[idx + run_len] - d_prev <= tol) {
+					pd0[idx + run_len] = d_prev;
+					rl[idx + run_len] = 0;
+					++run_len;
+				}
+				rl[idx] = run_len;
+				if (run_len > 1) {
+					applied_sh = 1;
+					T *hh = w.hh + off + idx, *zr = pz0 + idx;
+					T head = zr[run_len - 1];
+					T tn = 0;
+					for (int t = 0; t < run_len - 1; ++t)
+						tn += zr[t] * zr[t];
+					tn = ev_sqrt(tn);
+					T head_norm = ev_abs(head);
+					if (head_norm < sml) {
+						head = 0;
+						head_norm = 0;
+					}
+					T tau;
+					if (tn < sml) {
+						// make_householder_in_place: tau = inf, the reflector is the identity
+						tau = ev_inf<T>();
+						for (int t = 0; t < run_len - 1; ++t)
+							hh[t] = zr[t];
+					} else {
+						const T nrm = ev_hypot(head_norm, tn);
+						const T sign = head_norm != (T) 0 ? head / head_norm : (T) 1;
+						const T signed_norm = sign * nrm;
+						const T hwb_inv = (T) 1 / (head + signed_norm);
+						for (int t = 0; t < run_len - 1; ++t)
+							hh[t] = zr[t] * hwb_inv;
+						head = -signed_norm;
+						const T q = tn * ev_abs(hwb_inv);
+						tau = (T) 0.5 * ((T) 1 + q * q);
+					}
+					for (int t = 0; t < run_len - 1; ++t)
+						zr[t] = 0;
+					zr[run_len - 1] = head;
+					hh[run_len - 1] = tau;
+				}
+				idx += run_len;
+				if (idx >= n || rl[idx] != 0)
+					break;
+			}
+		}
+	}
+	__syncthreads();
+	// stable compaction: the k entries with z != 0 first, the deflated ones after them (:453-476)
+	const int chunk = (n + 255) / 256;
+	const int c0 = tid * chunk < n ? tid * chunk : n, c1 = c0 + chunk < n ? c0 + chunk : n;
+	int cnt = 0;
+	if (!all_deflated)
+		for (int i = c0; i < c1; ++i)
+			cnt += pz0[i] != (T) 0;
+	scan[tid + 1] = cnt;
+	__syncthreads();
+	if (tid == 0) {
+		scan[0] = 0;
+		for (int t = 1; t <= 256; ++t)
+			scan[t] += scan[t - 1];
+	}
+	__syncthreads();
+	const int k = scan[256];
+	int wn = scan[tid], wd = k + (c0 - scan[tid]);
+	for (int i = c0; i < c1; ++i) {
+		const T zv = pz0[i];
+		if (!all_deflated && zv != (T) 0) {
+			w.pd[off + wn] = pd0[i];
+			w.pz[off + wn] = zv;
+			w.pla[off + wn] = i;
+			++wn;
+		} else {
+			w.pd[off + wd] = pd0[i];
+			w.pla[off + wd] = i;
+			++wd;
+		}
+	}
+	if (tid == 0) {
+		w.k[b] = k;
+		w.applied[b] = all_deflated ? 0 : applied_sh;
+		w.rho[b] = rho;
+	}
+}
+
+// secular_eq_root_finder (svd/bidiag_svd.rs:7-270) evaluated by a whole wavefront; every lane holds the same scalars
+template <typename T> struct SecularEq {
+	const T *d, *z;
+	int k;
+	T rho_recip;
+	__device__ T operator()(T shift, T mu) const
+	{
+		T acc = 0;
+		for (int i = (int) (threadIdx.x & 63); i < k; i += 64) {
+			const T zi = z[i];
+			acc += zi * (zi / ((d[i] - shift) - mu));
+		}
+		return rho_recip + wave_sum(acc);
+	}
+};
+
+template <typename T, typename F> __device__ void secular_root(const F &f, T left, T right, bool last, T &shift_out, T &mu_out)
+{
+	const T two = 2, eight = 8, one_half = 0.5, epsilon = EvdTraits<T>::eps;
+	// loop caps: none is reached by a convergent search, they only keep a non-finite input from spinning
+	constexpr int SECANT_CAP = 256, BISECT_CAP = 2200;
+	const T mid = left + (right - left) * one_half;
+	T f_mid = f((T) 0, mid);
+	const T f_max = f(left, last ? right - left : (right - left) * one_half);
+	const T f_mid_left_shift = f(left, (right - left) * one_half);
+	const T f_mid_right_shift = f(right, (left - right) * one_half);
+	T shift, mu;
+	if (last || f_mid > (T) 0) {
+		shift = left;
+		mu = (right - left) * one_half;
+	} else {
+		shift = right;
+		mu = (left - right) * one_half;
+	}
+	if (f_mid_left_shift <= (T) 0 && f_mid_right_shift > (T) 0) {
+		shift_out = shift;
+		mu_out = mu;
+		return;
+	}
+	if (!last) {
+		if (shift == left) {
+			if (f_mid_left_shift < (T) 0) {
+				shift = right;
+				f_mid = f_mid_right_shift;
+			}
+		} else if (f_mid_right_shift > (T) 0) {
+			shift = left;
+			f_mid = f_mid_left_shift;
+		}
+	}
+	T left_shifted, f_left, right_shifted, f_right;
+	if (shift == left) {
+		left_shifted = 0;
+		f_left = -ev_inf<T>();
+		right_shifted = last ? right - left : (right - left) * one_half;
+		f_right = last ? f_max : f_mid;
+	} else {
+		left_shifted = (left - right) * one_half;
+		f_left = f_mid;
+		right_shifted = 0;
+		f_right = ev_inf<T>();
+	}
+	int iteration_count = 0;
+	T f_prev = f_mid;
+	const T half0 = one_half, half1 = half0 * half0, half2 = half1 * half1, half3 = half2 * half2;
+	const T base = shift == left ? right_shifted : left_shifted;
+	const T mu_values[4] = {base * half3, base * half2, base * half1, base * half0};
+	T f_values[4];
+	for (int t = 0; t < 4; ++t)
+		f_values[t] = f(shift, mu_values[t]);
+	if (shift == left) {
+		int i = 0;
+		for (int t = 0; t < 4; ++t)
+			if (f_values[t] < (T) 0) {
+				left_shifted = mu_values[t];
+				f_left = f_values[t];
+				i = t + 1;
+			}
+		if (i < 4) {
+			right_shifted = mu_values[i];
+			f_right = f_values[i];
+		}
+	} else {
+		int i = 0;
+		for (int t = 0; t < 4; ++t)
+			if (f_values[t] > (T) 0) {
+				right_shifted = mu_values[t];
+				f_right = f_values[t];
+				i = t + 1;
+			}
+		if (i < 4) {
+			left_shifted = mu_values[i];
+			f_left = f_values[i];
+		}
+	}
+	while (right_shifted - left_shifted > two * epsilon * ev_max(ev_abs(left_shifted), ev_abs(right_shifted))) {
+		const T mid_a = (left_shifted + right_shifted) * one_half;
+		T mid_g = ev_sqrt(ev_abs(left_shifted)) * ev_sqrt(ev_abs(right_shifted));
+		if (left_shifted < (T) 0)
+			mid_g = -mid_g;
+		const T mid_shifted = mid_g == (T) 0 ? mid_a : mid_g;
+		const T fm = f(shift, mid_shifted);
+		if (fm == (T) 0) {
+			shift_out = shift;
+			mu_out = mid_shifted;
+			return;
+		} else if (fm > (T) 0) {
+			right_shifted = mid_shifted;
+			f_prev = f_right;
+			f_right = fm;
+		} else {
+			left_shifted = mid_shifted;
+			f_prev = f_left;
+			f_left = fm;
+		}
+		if (iteration_count == 4)
+			break;
+		++iteration_count;
+	}
+	T mu_cur, mu_prev, f_cur, f_prv;
+	if (left_shifted == (T) 0) {
+		mu_cur = right_shifted * two;
+		mu_prev = right_shifted;
+		f_cur = f_prev;
+		f_prv = f_right;
+	} else if (right_shifted == (T) 0) {
+		mu_cur = left_shifted * two;
+		mu_prev = left_shifted;
+		f_cur = f_prev;
+		f_prv = f_left;
+	} else {
+		mu_cur = left_shifted;
+		mu_prev = right_shifted;
+		f_cur = f_left;
+		f_prv = f_right;
+	}
+	// secant (bidiag_svd.rs:56-126)
+	if (ev_abs(f_prv) < ev_abs(f_cur)) {
+		T t = f_prv;
+		f_prv = f_cur;
+		f_cur = t;
+		t = mu_prev;
+		mu_prev = mu_cur;
+		mu_cur = t;
+	}
+	bool has_l = false, has_r = false, use_bisection = false;
+	T lc = 0, rcand = 0;
+	if ((f_prv > (T) 0) != (f_cur > (T) 0)) {
+		lc = mu_cur < mu_prev ? mu_cur : mu_prev;
+		rcand = mu_cur < mu_prev ? mu_prev : mu_cur;
+		has_l = has_r = true;
+	}
+	for (int it = 0; it < SECANT_CAP && f_cur != (T) 0 &&
+			 ev_abs(mu_cur - mu_prev) > eight * epsilon * ev_max(ev_abs(mu_cur), ev_abs(mu_prev)) && ev_abs(f_cur - f_prv) > epsilon &&
+			 !use_bisection;
+	     ++it) {
+		const T a = (f_cur - f_prv) * (mu_prev * mu_cur) / (mu_prev - mu_cur);
+		const T bb = f_cur - a / mu_cur;
+		const T mu_zero = -a / bb;
+		const T f_zero = f(shift, mu_zero);
+		if (f_zero < (T) 0) {
+			lc = mu_zero;
+			has_l = true;
+		} else {
+			rcand = mu_zero;
+			has_r = true;
+		}
+		mu_prev = mu_cur;
+		f_prv = f_cur;
+		mu_cur = mu_zero;
+		f_cur = f_zero;
+		if (shift == left && (mu_cur < (T) 0 || mu_cur > right - left))
+			use_bisection = true;
+		if (shift == right && (mu_cur > (T) 0 || mu_cur < left - right))
+			use_bisection = true;
+		if (ev_abs(f_cur) > ev_abs(f_prv)) {
+			T kk = 1;
+			for (int t = 0; t < 4; ++t) {
+				const T mu_opp = -a / (kk * f_zero + bb);
+				const T f_opp = f(shift, mu_opp);
+				if (f_zero < (T) 0 && f_opp >= (T) 0) {
+					rcand = mu_opp;
+					has_r = true;
+					break;
+				}
+				if (f_zero > (T) 0 && f_opp <= (T) 0) {
+					lc = mu_opp;
+					has_l = true;
+					break;
+				}
+				kk = kk * two;
+			}
+			use_bisection = true;
+		}
+	}
+	if (has_l && has_r && lc < rcand) {
+		if (lc > left_shifted)
+			left_shifted = lc;
+		if (rcand < right_shifted)
+			right_shifted = rcand;
+	}
+	if (use_bisection) {
+		for (int it = 0; it < BISECT_CAP && right_shifted - left_shifted > two * epsilon * ev_max(ev_abs(left_shifted), ev_abs(right_shifted));
+		     ++it) {
+			const T mid_shifted = (left_shifted + right_shifted) * one_half;
+			const T fm = f(shift, mid_shifted);
+			if (fm == (T) 0)
+				break;
+			else if (fm > (T) 0)
+				right_shifted = mid_shifted;
+			else
+				left_shifted = mid_shifted;
+		}
+		mu_cur = (left_shifted + right_shifted) * one_half;
+	}
+	shift_out = shift;
+	mu_out = mu_cur;
+}
+
+// compute_eigenvalues (tridiag_evd.rs:233-268): one wavefront per root; grid (ceil(max n / 4), merges)
+template <typename T> __global__ __launch_bounds__(256) void evd_secular_kernel(const int *merges, EvdWork<T> w, const int *status)
+{
+	if (status[0])
+		return;
+	const int b = blockIdx.y;
+	const idx_t off = merges[3 * b];
+	const int n = merges[3 * b + 1];
+	const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (i >= n)
+		return;
+	const int k = w.k[b];
+	if (i >= k) {
+		if ((threadIdx.x & 63) == 0) {
+			w.sh[off + i] = 0;
+			w.mu[off + i] = w.pd[off + i];
+		}
+		return;
+	}
+	const T rho = w.rho[b];
+	const T *d = w.pd + off, *z = w.pz + off;
+	const bool last = i == k - 1;
+	T right;
+	if (last) {
+		T acc = 0;
+		for (int t = (int) (threadIdx.x & 63); t < k; t += 64)
+			acc += z[t] * z[t];
+		right = d[i] + rho * wave_sum(acc);
+	} else {
+		right = d[i + 1];
+	}
+	SecularEq<T> f{d, z, k, (T) 1 / rho};
+	T shift, mu;
+	secular_root<T>(f, d[i], right, last, shift, mu);
+	if ((threadIdx.x & 63) == 0) {
+		w.sh[off + i] = shift;
+		w.mu[off + i] = mu;
+	}
+}
+
+// Loewner z-hat (:497-511) and the ascending order of the merged eigenvalues (:516-533); grid (ceil(max n / 256), merges)
+template <typename T> __global__ __launch_bounds__(256) void evd_loewner_kernel(const int *merges, EvdWork<T> w, T *D, const int *status)
+{
+	if (status[0])
+		return;
+	const int b = blockIdx.y;
+	const idx_t off = merges[3 * b];
+	const int n = merges[3 * b + 1];
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n)
+		return;
+	const int k = w.k[b];
+	const T *mu = w.mu + off, *sh = w.sh + off, *d = w.pd + off;
+	if (i < k) {
+		const T di = d[i];
+		T prod = mu[i] + (sh[i] - di);
+		for (int t = 0; t < k; ++t)
+			if (t != i)
+				prod *= (mu[t] + (sh[t] - di)) / (d[t] - di);
+		prod = ev_sqrt(ev_abs(prod));
+		w.zh[off + i] = w.pz[off + i] < (T) 0 ? -prod : prod;
+	}
+	const T lam = mu[i] + sh[i];
+	int rank = 0;
+	for (int t = 0; t < n; ++t) {
+		const T lt = mu[t] + sh[t];
+		rank += (lt < lam) || (lt == lam && t < i);
+	}
+	w.pr[off + rank] = i;
+	D[off + rank] = lam;
+}
+
+// repaired_u (:534-592) in the final column order; grid (max n, merges), one column per workgroup.  Q is N x N column major
+// (ld N), the merge owns the diagonal block at (off, off).
+template <typename T> __global__ __launch_bounds__(256) void evd_qhat_kernel(const int *merges, EvdWork<T> w, T *Q, idx_t ldq, const int *status)
+{
+	__shared__ T red[4];
+	if (status[0])
+		return;
+	const int b = blockIdx.y, j = blockIdx.x, tid = threadIdx.x;
+	const idx_t off = merges[3 * b];
+	const int n = merges[3 * b + 1];
+	if (j >= n)
+		return;
+	const int k = w.k[b], pj = w.pr[off + j];
+	const int *pla = w.pla + off, *plb = w.plb + off;
+	T *q = Q + off + (off + j) * ldq;
+	if (pj >= k) {
+		for (int i = tid; i < n; i += 256)
+			q[plb[pla[i]]] = i == pj ? (T) 1 : (T) 0;
+	} else {
+		const T mu = w.mu[off + pj], sh = w.sh[off + pj];
+		const T *zh = w.zh + off, *d = w.pd + off;
+		// norm_l2 with a scale: an entry next to a pole may be huge
+		T mx = 0;
+		for (int i = tid; i < k; i += 256)
+			mx = ev_max(mx, ev_abs(zh[i] / ((d[i] - sh) - mu)));
+		mx = block_reduce<T, true>(mx, red);
+		const T inv_mx = mx > (T) 0 ? (T) 1 / mx : (T) 1;
+		T ss = 0;
+		for (int i = tid; i < k; i += 256) {
+			const T v = (zh[i] / ((d[i] - sh) - mu)) * inv_mx;
+			ss += v * v;
+		}
+		ss = block_reduce<T, false>(ss, red);
+		const T inv_norm = (T) 1 / (mx * ev_sqrt(ss));
+		for (int i = tid; i < n; i += 256)
+			q[plb[pla[i]]] = i < k ? (zh[i] / ((d[i] - sh) - mu)) * inv_norm : (T) 0;
+	}
+	if (!w.applied[b])
+		return;
+	__syncthreads(); // the column's entries written by the other threads of the block
+	// the run reflectors (:566-590); rows are in pl_before order, so row r of the picture sits at q[plb[r]]
+	const int *rl = w.rl + off;
+	const T *hh = w.hh + off;
+	for (int r = tid; r < n; r += 256) {
+		const int len = rl[r];
+		if (len <= 1)
+			continue;
+		const T tau_inv = (T) 1 / hh[r + len - 1];
+		T dot = 0;
+		for (int t = 0; t < len; ++t)
+			dot += (t + 1 < len ? hh[r + t] : (T) 1) * q[plb[r + t]];
+		dot *= tau_inv;
+		for (int t = 0; t < len; ++t)
+			q[plb[r + t]] -= dot * (t + 1 < len ? hh[r + t] : (T) 1);
+	}
+}
+
+template <typename T> __global__ void evd_write_s_kernel(const T *D, idx_t n, T *S, idx_t ss, const T *fac) // fac: {A scale, T scale}
+{
+	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n)
+		S[i * ss] = D[i] * ((T) 1 / fac[0]) * ((T) 1 / fac[1]);
+}
+
+struct EvdNode {
+	idx_t off, n;
+	int depth;
+};
+
+void evd_plan(idx_t off, idx_t n, int depth, idx_t leaf, std::vector<EvdNode> &leaves, std::vector<std::vector<EvdNode>> &merges)
+{
+	if (n <= leaf) {
+		leaves.push_back(EvdNode{off, n, depth});
+		return;
+	}
+	if ((int) merges.size() <= depth)
+		merges.resize((size_t) depth + 1);
+	merges[(size_t) depth].push_back(EvdNode{off, n, depth});
+	const idx_t n1 = n / 2;
+	evd_plan(off, n1, depth + 1, leaf, leaves, merges);
+	evd_plan(off + n1, n - n1, depth + 1, leaf, leaves, merges);
+}
+
+inline unsigned blocks_for(idx_t count, int per) { return (unsigned) ((count + per - 1) / per); }
+
+} // namespace
+
+// Leaves of min(max(recursion_threshold, 4), 64) rows.  The leaf kernel holds up to EVD_LEAF_MAX = 128 rows, but lane 0's
+// Givens chain grows as the square of the leaf size while the merge level that 64-row leaves add is cheap: at N = 4096 fp64
+// the solve takes 8.8 ms with 64-row leaves against 15.8 ms with 128-row ones (32: 8.6).
+constexpr size_t EVD_LEAF_CLAMP = 64;
+idx_t evd_leaf_size(size_t recursion_threshold)
+{
+	const size_t t = recursion_threshold < 4 ? 4 : recursion_threshold;
+	return (idx_t) (t > EVD_LEAF_CLAMP ? EVD_LEAF_CLAMP : t);
+}
+
+template <typename T> int self_adjoint_evd_dev(MatV<const T> A, MatV<T> U, T *S, idx_t ss, idx_t leaf, idx_t bs)
+{
+	const idx_t n = A.nrows;
+	FH_CHECK(A.ncols == n && n > 0, "self_adjoint_evd: the matrix must be square and not empty");
+	FH_CHECK(n < (1L << 30), "self_adjoint_evd: matrix too large");
+	FH_CHECK(leaf >= 4 && leaf <= EVD_LEAF_MAX, "self_adjoint_evd: leaf size out of range");
+	hipStream_t s = ctx().stream;
+	const bool want_u = U.p != nullptr;
+
+	// plan of the recursion (host, from n alone)
+	std::vector<EvdNode> leaves;
+	std::vector<std::vector<EvdNode>> merges;
+	evd_plan(0, n, 0, leaf, leaves, merges);
+	const int levels = (int) merges.size();
+	std::vector<int> tab;
+	for (const EvdNode &l : leaves) {
+		tab.push_back((int) l.off);
+		tab.push_back((int) l.n);
+		tab.push_back(l.depth & 1);
+	}
+	std::vector<size_t> level_at((size_t) levels);
+	size_t nmerges = 0, max_level = 0;
+	for (int lv = 0; lv < levels; ++lv) {
+		level_at[(size_t) lv] = tab.size();
+		nmerges += merges[(size_t) lv].size();
+		max_level = std::max(max_level, merges[(size_t) lv].size());
+		for (const EvdNode &m : merges[(size_t) lv]) {
+			tab.push_back((int) m.off);
+			tab.push_back((int) m.n);
+			tab.push_back((int) (m.n / 2));
+		}
+	}
+	FH_CHECK(leaves.size() < (1u << 31) && max_level < 65536, "self_adjoint_evd: too many nodes");
+
+	// device memory: the reduced matrix, its block factors, two eigenvector buffers (depth parity), Qhat, the work vectors
+	const size_t nn = (size_t) n * (size_t) n;
+	Scratch trid(nn * sizeof(T)), hb((size_t) bs * (size_t) (n > 1 ? n - 1 : 1) * sizeof(T));
+	Scratch ub0(want_u ? 16 : nn * sizeof(T)), ub1(levels > 0 ? nn * sizeof(T) : 16), qb(levels > 0 ? nn * sizeof(T) : 16);
+	Scratch vec((size_t) 12 * (size_t) n * sizeof(T) + (size_t) (4 * n + 2 * (n + 1)) * sizeof(int) + 64), tb(tab.size() * sizeof(int) + 16),
+		stb(16 * sizeof(int));
+	int *status = stb.as<int>();
+	T *D = vec.as<T>(), *E = D + n;
+	EvdWork<T> w;
+	{
+		T *p = E + n;
+		T **tp[] = {&w.z, &w.pd0, &w.pz0, &w.pd, &w.pz, &w.hh, &w.mu, &w.sh, &w.zh, &w.rho};
+		for (T **q : tp) {
+			*q = p;
+			p += n;
+		}
+		int *ip = reinterpret_cast<int *>(p);
+		int **ipp[] = {&w.plb, &w.pla, &w.rl, &w.pr};
+		for (int **q : ipp) {
+			*q = ip;
+			ip += n;
+		}
+		w.k = ip;
+		w.applied = ip + (n + 1);
+	}
+	int *tab_dev = tb.as<int>();
+	FH_HIP(hipMemsetAsync(status, 0, 16 * sizeof(int), s));
+	FH_HIP(hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+
+	// 1-3: T = Q^H lower(A) Q, diag / offdiag (mod.rs:326-356)
+	MatV<T> X{trid.as<T>(), n, n, 1, n};
+	typedef typename EvdBits<T>::U Bits;
+	Bits *amax = reinterpret_cast<Bits *>(status + 4); // {max |lower(A)|, max(|d|, |e|)}
+	T *fac = reinterpret_cast<T *>(status + 8);	    // their power-of-two factors
+	hipLaunchKernelGGL(evd_copy_lower_kernel<T>, dim3(blocks_for((idx_t) nn, 256)), dim3(256), 0, s, A.p, A.rs, A.cs, X.p, n, amax);
+	hipLaunchKernelGGL(evd_scale_kernel<T>, dim3(blocks_for((idx_t) nn, 256)), dim3(256), 0, s, X.p, (idx_t) nn, (const Bits *) amax, fac);
+	MatV<T> H{hb.as<T>(), bs, n - 1, 1, bs};
+	if (n > 1)
+		tridiag_dev<T>(X, H);
+	hipLaunchKernelGGL(evd_extract_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, X.p, n, D, E, amax + 1, status);
+	hipLaunchKernelGGL(evd_tscale_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, D, E, n, (const Bits *) (amax + 1), fac + 1);
+
+	// 4: tridiagonal divide and conquer (U buffer of depth d: d even -> u0, odd -> u1; the root writes u0)
+	MatV<T> u0 = want_u ? U : MatV<T>{ub0.as<T>(), n, n, 1, n};
+	MatV<T> u1{ub1.as<T>(), n, n, 1, n};
+	if (nmerges > 0)
+		hipLaunchKernelGGL(evd_tear_kernel<T>, dim3(blocks_for((idx_t) nmerges, 256)), dim3(256), 0, s, tab_dev + level_at[0],
+				   (int) nmerges, D, E, status);
+	{
+		static std::atomic<unsigned long long> attr_done{0}; // bit d: device d (the attribute is per device)
+		const int dev = ctx().device;
+		const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
+		const size_t lds = evd_leaf_lds<T>(EVD_LEAF_MAX);
+		if (bit == 0 || !(attr_done.load(std::memory_order_acquire) & bit)) {
+			FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&evd_leaf_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+			attr_done.fetch_or(bit, std::memory_order_release);
+		}
+		hipLaunchKernelGGL(evd_leaf_kernel<T>, dim3((unsigned) leaves.size()), dim3(64), evd_leaf_lds<T>((int) leaf), s, tab_dev, D, E, u0.p,
+				   u0.rs, u0.cs, u1.p, u1.rs, u1.cs, status);
+	}
+	MatV<T> Q{qb.as<T>(), n, n, 1, n};
+	for (int lv = levels - 1; lv >= 0; --lv) {
+		const std::vector<EvdNode> &ms = merges[(size_t) lv];
+		const int *mt = tab_dev + level_at[(size_t) lv];
+		const unsigned cnt = (unsigned) ms.size();
+		idx_t maxn = 0;
+		for (const EvdNode &m : ms)
+			maxn = std::max(maxn, m.n);
+		const MatV<T> src = (lv & 1) ? u0 : u1, dst = (lv & 1) ? u1 : u0; // children at depth lv + 1
+		hipLaunchKernelGGL(evd_merge_prep_kernel<T>, dim3(cnt), dim3(256), 0, s, mt, (const T *) D, (const T *) E, (const T *) src.p, src.rs,
+				   src.cs, w, status);
+		hipLaunchKernelGGL(evd_secular_kernel<T>, dim3(blocks_for(maxn, 4), cnt), dim3(256), 0, s, mt, w, status);
+		hipLaunchKernelGGL(evd_loewner_kernel<T>, dim3(blocks_for(maxn, 256), cnt), dim3(256), 0, s, mt, w, D, status);
+		hipLaunchKernelGGL(evd_qhat_kernel<T>, dim3((unsigned) maxn, cnt), dim3(256), 0, s, mt, w, Q.p, n, status);
+		FH_HIP(hipGetLastError());
+		for (const EvdNode &m : ms) {
+			const idx_t o = m.off, n1 = m.n / 2, n2 = m.n - n1;
+			gemm_dev<T>(dst.sub(o, o, n1, m.n), DST_FULL, false, src.sub(o, o, n1, n1).c(), Q.sub(o, o, n1, m.n).c(), (T) 1);
+			gemm_dev<T>(dst.sub(o + n1, o, n2, m.n), DST_FULL, false, src.sub(o + n1, o + n1, n2, n2).c(), Q.sub(o + n1, o, n2, m.n).c(),
+				    (T) 1);
+		}
+	}
+
+	// 5: U[1:, :] <- Q_tridiag U[1:, :] (mod.rs:410-418)
+	if (want_u && n > 1)
+		apply_householder_sequence_left_dev<T>(X.sub(1, 0, n - 1, n - 1).c(), H.c(), U.sub(1, 0, n - 1, n), false);
+	// 6: S
+	hipLaunchKernelGGL(evd_write_s_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const T *) D, n, S, ss, (const T *) fac);
+	FH_HIP(hipGetLastError());
+	int *st = ctx().pinned_ints();
+	FH_HIP(hipMemcpyAsync(st, status, sizeof(int), hipMemcpyDeviceToHost, s));
+	FH_HIP(hipStreamSynchronize(s)); // also keeps `tab` alive until its copy has run
+	return st[0];
+}
+
+template int self_adjoint_evd_dev<double>(MatV<const double>, MatV<double>, double *, idx_t, idx_t, idx_t);
+template int self_adjoint_evd_dev<float>(MatV<const float>, MatV<float>, float *, idx_t, idx_t, idx_t);
+
+} // namespace fh

@@ -119,6 +119,18 @@ typedef struct FaerFullPivLuStatus {
 	};
 } FaerFullPivLuStatus;
 typedef struct FaerQrParams { size_t blocking_threshold; size_t par_threshold; } FaerQrParams;
+/* self-adjoint EVD: faer.h:191-194, :260-279, lib.rs:2368-2400 (evd/mod.rs:82-88, evd/tridiag.rs:15-20) */
+typedef enum FaerComputeEigenvectors { FaerComputeEigenvectors_No = 0, FaerComputeEigenvectors_Yes = 1 } FaerComputeEigenvectors;
+typedef struct FaerTridiagParams { size_t par_threshold; } FaerTridiagParams;
+typedef struct FaerSelfAdjointEvdParams { FaerTridiagParams tridiag; size_t recursion_threshold; } FaerSelfAdjointEvdParams;
+typedef enum FaerEvdStatus_Tag { FaerEvdStatus_Ok = 0, FaerEvdStatus_NoConvergence = 1 } FaerEvdStatus_Tag;
+typedef struct FaerEvdStatus {
+	FaerEvdStatus_Tag tag;
+	union {
+		struct { size_t padding; } ok;
+		struct { size_t padding; } no_convergence;
+	};
+} FaerEvdStatus;
 /* faer-ffi/src/lib.rs:796-801; pointers to a real scalar of the matrix dtype (HOST memory), NULL == 0 */
 typedef struct FaerLltRegularization { const void *dynamic_regularization_delta; const void *dynamic_regularization_epsilon; } FaerLltRegularization;
 /* lib.rs:820-828: signs is a slice of i8 (HOST memory, `dim` entries) or a null ptr */
@@ -444,6 +456,25 @@ FAER_HIP_API FaerLayout libfaer_v0_23_colpiv_qr_reconstruct_scratch_u64_f32(size
 FAER_HIP_API void libfaer_v0_23_colpiv_qr_reconstruct_u64_f32(FaerMatMut A, FaerMatRef Q_basis, FaerMatRef Q_coeff, FaerMatRef R, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
 FAER_HIP_API FaerLayout libfaer_v0_23_colpiv_qr_inverse_scratch_u64_f32(size_t dim, size_t block_size, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_colpiv_qr_inverse_u64_f32(FaerMatMut A_inv, FaerMatRef Q_basis, FaerMatRef Q_coeff, FaerMatRef R, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+/* ---------------------------------------------------------------------------------------------
+ * 2e. Self-adjoint eigendecomposition (faer-ffi/src/lib.rs:2368-2400; evd/mod.rs:270-425): A = U diag(S) U^H.
+ *     A (n x n): only its lower triangle is read, A is never written.  S (n entries) receives the eigenvalues in
+ *     ascending order.  U.ncols == 0: no eigenvectors; otherwise U is n x n and column j is the unit eigenvector of
+ *     S[j].  Tridiagonalization (csrc/qr.hip), divide and conquer on the tridiagonal with QR-iteration leaves
+ *     (csrc/evd.hip), block Householder back-transform.  Leaves hold at most min(max(recursion_threshold, 4), 64) rows:
+ *     a larger threshold is clamped to 64 (the decomposition is the same up to rounding).  par, mem and
+ *     params.tridiag are accepted and ignored.  NoConvergence: a non-finite entry in the tridiagonal form, or a leaf
+ *     over the reference's iteration cap.  Host or device operands, any strides.
+ * --------------------------------------------------------------------------------------------- */
+FAER_HIP_API FaerTridiagParams libfaer_v0_23_TridiagParams_f64(void);
+FAER_HIP_API FaerTridiagParams libfaer_v0_23_TridiagParams_f32(void);
+FAER_HIP_API FaerSelfAdjointEvdParams libfaer_v0_23_SelfAdjointEvdParams_f64(void);
+FAER_HIP_API FaerSelfAdjointEvdParams libfaer_v0_23_SelfAdjointEvdParams_f32(void);
+FAER_HIP_API FaerLayout libfaer_v0_23_self_adjoint_evd_scratch_f64(size_t dim, FaerComputeEigenvectors compute_U, FaerPar par, FaerSelfAdjointEvdParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_self_adjoint_evd_scratch_f32(size_t dim, FaerComputeEigenvectors compute_U, FaerPar par, FaerSelfAdjointEvdParams params);
+FAER_HIP_API FaerEvdStatus libfaer_v0_23_self_adjoint_evd_f64(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerPar par, FaerMemAlloc mem, FaerSelfAdjointEvdParams params);
+FAER_HIP_API FaerEvdStatus libfaer_v0_23_self_adjoint_evd_f32(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerPar par, FaerMemAlloc mem, FaerSelfAdjointEvdParams params);
+
 #endif /* FAER_HIP_NO_FFI_PROTOTYPES */
 
 /* ---------------------------------------------------------------------------------------------
