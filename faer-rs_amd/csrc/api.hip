@@ -1469,6 +1469,17 @@ int faer_hip_debug_dist_two_streams_ok(size_t panel_rows, FaerHipDType dtype, in
 void faer_hip_debug_lu_force_general(int on) { lu_force_general(on); }
 void faer_hip_debug_lu_plan(size_t nb2_from, size_t pipe_from, size_t la_min_cols) { lu_debug_plan((long) nb2_from, (long) pipe_from, (long) la_min_cols); }
 long faer_hip_debug_qr_one_pass_columns(void) { return qr_last_one_pass_columns(); }
+void faer_hip_debug_route_reset(void)
+{
+	for (long long &c : g_route_counts)
+		c = 0;
+}
+size_t faer_hip_debug_route_counts(long long *out, size_t cap)
+{
+	for (size_t i = 0; i < cap && i < (size_t) FaerHipRoute_Count; ++i)
+		out[i] = g_route_counts[i];
+	return (size_t) FaerHipRoute_Count;
+}
 void faer_hip_debug_qr_panel_copy(int on) { tsqr_debug_panel_copy(on); }
 void faer_hip_debug_qr_one_pass_f64(int on) { tsqr_debug_f64(on); }
 void faer_hip_debug_qr_panels_one_pass(int on) { tsqr_debug_panels(on); }

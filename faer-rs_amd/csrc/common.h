@@ -324,6 +324,10 @@ template <typename T> struct GemmExtra {
 	bool prefer_big_tiles = false;
 };
 
+// route counters of the GEMM / TRSM dispatch (faer_hip_debug_route_counts): thread-local, defined in gemm.hip
+extern thread_local long long g_route_counts[FaerHipRoute_Count];
+static inline void route_hit(FaerHipRoute r) { ++g_route_counts[r]; }
+
 // dst(kind) <- [dst +] alpha * A * diag * B        (gemm.hip)
 template <typename T>
 void gemm_dev(MatV<T> C, DstKind kind, bool add, MatV<const T> A, MatV<const T> B, T alpha,

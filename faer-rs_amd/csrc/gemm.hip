@@ -1156,6 +1156,8 @@ template <typename T, int BM, int BN, int WM, int WN> static void launch_cfg_p(c
 	FH_HIP(hipGetLastError());
 }
 
+thread_local long long g_route_counts[FaerHipRoute_Count];
+
 template <typename T>
 void gemm_dev(MatV<T> C, DstKind kind, bool add, MatV<const T> A, MatV<const T> B, T alpha, const GemmExtra<T> *extra)
 {
@@ -1164,6 +1166,7 @@ void gemm_dev(MatV<T> C, DstKind kind, bool add, MatV<const T> A, MatV<const T> 
 	if (m == 0 || n == 0)
 		return;
 	if (k == 0) { // faer/src/linalg/matmul/mod.rs:1190-1198
+		route_hit(FaerHipRoute_GemmZeroK);
 		if (!add)
 			fill_ext<T>(C, kind, (T) 0, extra);
 		return;
@@ -1175,21 +1178,25 @@ void gemm_dev(MatV<T> C, DstKind kind, bool add, MatV<const T> A, MatV<const T> 
 	// level-2 shapes leave for the streaming kernels (matmul/mod.rs:1215-1310: matvec / rank_update dispatch)
 	if (kind == DST_FULL && !ex.row_idx && !ex.col_idx && !ex.diag && !ex.a_struct && !ex.b_struct && !ex.inplace) {
 		if (k == 1 && m * n >= 1) {
+			route_hit(FaerHipRoute_GemmRank1);
 			rank1_dev<T>(C, add, A.p, A.rs, B.p, B.cs, alpha);
 			return;
 		}
-		if (n == 1 && gemv_dev<T>(m, k, A, B.p, B.rs, C.p, C.rs, alpha, add))
+		if ((n == 1 && gemv_dev<T>(m, k, A, B.p, B.rs, C.p, C.rs, alpha, add)) || (m == 1 && gemv_dev<T>(n, k, B.t(), A.p, A.cs, C.p, C.cs, alpha, add))) {
+			route_hit(FaerHipRoute_GemmGemv);
 			return;
-		if (m == 1 && gemv_dev<T>(n, k, B.t(), A.p, A.cs, C.p, C.cs, alpha, add))
-			return;
+		}
 		// one dimension huge, the other two tiny: HBM streams as well (block-reflector steps of a tall QR)
-		if (skinny_dev<T>(C, add, A, B, alpha))
+		if (skinny_dev<T>(C, add, A, B, alpha)) {
+			route_hit(FaerHipRoute_GemmSkinny);
 			return;
+		}
 	}
 	const bool indexed = ex.row_idx || ex.col_idx;
 	// Upper(dst) == Lower(dst^T); dst^T = B^T diag A^T.  Also prefer the unit dst stride along m.
 	bool transpose = (kind == DST_UPPER) || (kind == DST_FULL && iabs(C.cs) == 1 && iabs(C.rs) != 1 && !indexed);
 	if (transpose) {
+		route_hit(FaerHipRoute_GemmTransposed);
 		MatV<T> Ct = C.t();
 		MatV<const T> At = B.t(), Bt = A.t();
 		C = Ct;
@@ -1297,6 +1304,7 @@ void gemm_dev(MatV<T> C, DstKind kind, bool add, MatV<const T> A, MatV<const T> 
 				// rectangle below the skipped rows, then the lower triangle right of it, as two plain products.
 				const idx_t sk = ex.tri_skip;
 				FH_CHECK(kind == DST_LOWER && m == n && sk < m, "gemm: tri_skip needs a square lower dst");
+				route_hit(FaerHipRoute_GemmTriSkipSplit);
 				gemm_dev<T>(C.sub(sk, 0, m - sk, sk), DST_FULL, add, A.sub(sk, 0, m - sk, k), B.sub(0, 0, k, sk), alpha, nullptr);
 				gemm_dev<T>(C.sub(sk, sk, m - sk, m - sk), DST_LOWER, add, A.sub(sk, 0, m - sk, k), B.sub(0, sk, k, m - sk), alpha, nullptr);
 				return;
@@ -1411,6 +1419,18 @@ void gemm_dev(MatV<T> C, DstKind kind, bool add, MatV<const T> A, MatV<const T> 
 	prof.sp.d[1] = (long) n;
 	prof.sp.d[2] = (long) k;
 	prof.sp.d[3] = g.tri_enum ? 1 + (long) ex.tri_skip : 0;
+	if (g.tri_enum)
+		route_hit(FaerHipRoute_GemmTriEnum);
+	if (splits > 1)
+		route_hit(FaerHipRoute_GemmSplitK);
+	if (g.fast_io)
+		route_hit(g.fast_io == 1 ? FaerHipRoute_GemmFastIo1 : g.fast_io == 2 ? FaerHipRoute_GemmFastIo2 : FaerHipRoute_GemmFastIo3);
+	route_hit(extra_path ? FaerHipRoute_GemmExtra64
+		  : shape == 5 ? FaerHipRoute_GemmPipeWide
+		  : shape == 2 ? FaerHipRoute_GemmInplace32x128
+		  : shape == 3 ? FaerHipRoute_GemmInplace128x32
+		  : legacy ? (shape == 0 ? FaerHipRoute_GemmLegacy128 : FaerHipRoute_GemmLegacy64)
+		  : shape == 0 ? FaerHipRoute_GemmPipe128 : FaerHipRoute_GemmPipe64);
 	if (extra_path)
 		launch_cfg<T, 64, 64, 2, 2, true>(g, akm, bkm, splits); // triangular operands / diag scaling
 	else if (shape == 5)

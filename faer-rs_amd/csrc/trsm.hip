@@ -557,6 +557,8 @@ template <typename T> static void trsm_leaf128_launch(const T *img, MatV<T> X, M
 	auto ab = [](idx_t v) { return v < 0 ? -v : v; };
 	const int along_rhs = ab(X.cs) <= ab(X.rs) ? 1 : 0;
 	const bool narrow = (k + TL_NW * 16 - 1) / (TL_NW * 16) <= (idx_t) ctx().stream_cus();
+	route_hit(img ? (narrow ? FaerHipRoute_TrsmLeafPacked16 : FaerHipRoute_TrsmLeafPacked32)
+		      : (narrow ? FaerHipRoute_TrsmLeafDirect16 : FaerHipRoute_TrsmLeafDirect32));
 	if (img) {
 		if (narrow)
 			trsm_leaf128_go<T, false, 16>(img, n, X, along_rhs, 0, 0, 0);
@@ -581,6 +583,7 @@ template <typename T> static void trsm_rec(MatV<const T> L, MatV<T> X, const T *
 			trsm_leaf128_launch<T>(nullptr, X, L, unit);
 		return;
 	}
+	route_hit(FaerHipRoute_TrsmRecursion);
 	const idx_t nblk = (n + TRSM_IB - 1) / TRSM_IB;
 	const idx_t top = (nblk / 2) * TRSM_IB;
 	MatV<T> Xt = X.sub(0, 0, top, k), Xb = X.sub(top, 0, n - top, k);
@@ -643,6 +646,7 @@ template <typename T> void trsm_lower_dev(MatV<const T> L, bool unit, MatV<T> X)
 	auto ab = [](idx_t v) { return v < 0 ? -v : v; };
 	const int along_rhs = ab(X.cs) <= ab(X.rs) ? 1 : 0;
 	FH_CHECK(k < (1L << 31), "trsm: too many right-hand sides");
+	route_hit(FaerHipRoute_TrsmTiny);
 	hipLaunchKernelGGL(trsm_leaf_kernel<T>, dim3((unsigned) ((k + 63) / 64)), dim3(64), 0, ctx().stream, L.p, L.rs, L.cs, (int) n,
 			   unit ? 1 : 0, X.p, X.rs, X.cs, (int) k, along_rhs);
 	FH_HIP(hipGetLastError());

@@ -521,6 +521,40 @@ FAER_HIP_API void faer_hip_debug_lu_plan(size_t nb2_from, size_t pipe_from, size
  * qr_factor_in_place (== ncols: the whole factorization; fewer: a panel was rejected and the classic path finished; -1: the
  * path was not applicable) */
 FAER_HIP_API long faer_hip_debug_qr_one_pass_columns(void);
+/* tests: which GEMM / TRSM routes the calling thread's library calls took.  One counter per route, thread-local, incremented
+ * once per launch decision of gemm_dev / the triangular solves (recursive calls count too; a product can count several routes:
+ * the transposed orientation, split-K and a fused epilogue next to its kernel's tile).  faer_hip_debug_route_counts copies at
+ * most `cap` counters in enum order and returns FaerHipRoute_Count. */
+typedef enum FaerHipRoute {
+	FaerHipRoute_GemmZeroK = 0,		/* K == 0: fill (Replace) or nothing (Add) */
+	FaerHipRoute_GemmRank1 = 1,		/* K == 1 stream */
+	FaerHipRoute_GemmGemv = 2,		/* N == 1 or M == 1 stream */
+	FaerHipRoute_GemmSkinny = 3,		/* one huge dimension, two tiny ones */
+	FaerHipRoute_GemmTransposed = 4,	/* Upper dst, or a row-major Full dst: the product runs on dst^T */
+	FaerHipRoute_GemmExtra64 = 5,		/* 64 x 64 kernel for structured operands, diag scaling, index scatter */
+	FaerHipRoute_GemmPipe64 = 6,		/* pipelined 64 x 64 tile */
+	FaerHipRoute_GemmPipe128 = 7,		/* pipelined 128 x 128 tile */
+	FaerHipRoute_GemmPipeWide = 8,		/* pipelined 128 x 256 tile (eight wavefronts) */
+	FaerHipRoute_GemmInplace32x128 = 9,	/* in-place product, 32 x 128 tile */
+	FaerHipRoute_GemmInplace128x32 = 10,	/* in-place product, 128 x 32 tile */
+	FaerHipRoute_GemmLegacy64 = 11,		/* non-pipelined 64 x 64 tile */
+	FaerHipRoute_GemmLegacy128 = 12,	/* non-pipelined 128 x 128 tile */
+	FaerHipRoute_GemmTriSkipSplit = 13,	/* tri_skip on operands the pipelined loaders cannot address: two plain products */
+	FaerHipRoute_GemmSplitK = 14,		/* K split over workgroups + the deterministic reduce */
+	FaerHipRoute_GemmTriEnum = 15,		/* square lower dst: only the tiles of the lower triangle are launched */
+	FaerHipRoute_GemmFastIo1 = 16,		/* fused epilogue: Replace */
+	FaerHipRoute_GemmFastIo2 = 17,		/* fused epilogue: Add, alpha == 1 */
+	FaerHipRoute_GemmFastIo3 = 18,		/* fused epilogue: Add, alpha == -1 */
+	FaerHipRoute_TrsmTiny = 19,		/* one-wavefront solve (n <= 64, k < 64) */
+	FaerHipRoute_TrsmLeafDirect16 = 20,	/* 128-row leaf packing its own triangle, 16 right-hand sides per wavefront */
+	FaerHipRoute_TrsmLeafDirect32 = 21,	/* same, 32 right-hand sides per wavefront */
+	FaerHipRoute_TrsmLeafPacked16 = 22,	/* 128-row leaf from a packed image (Cholesky), 16 per wavefront */
+	FaerHipRoute_TrsmLeafPacked32 = 23,	/* same, 32 per wavefront */
+	FaerHipRoute_TrsmRecursion = 24,	/* recursion node: two half solves and one GEMM */
+	FaerHipRoute_Count = 25
+} FaerHipRoute;
+FAER_HIP_API void faer_hip_debug_route_reset(void);
+FAER_HIP_API size_t faer_hip_debug_route_counts(long long *out, size_t cap);
 /* tests: 1 (default) = the fp32 one-pass QR path (csrc/tsqr.hip) keeps a raw copy of the panel for the launches that read it after V has
  * overwritten it, where the copy fits in 1 GiB; 0 = never (what matrices of more than 4.19 M rows run: V = P M as a launch of its own). */
 FAER_HIP_API void faer_hip_debug_qr_panel_copy(int on);

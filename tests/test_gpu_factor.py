@@ -5,21 +5,26 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from gpu_util import EPS, init_gpu, rnd, spd, to_dev, to_host
+from gpu_util import EPS, Routes, init_gpu, rnd, spd, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 
 
 # ------------------------------------------------------------------------------------------ trsm
-@pytest.mark.parametrize("n,k", [(1, 3), (4, 5), (7, 2), (33, 70), (64, 64), (65, 1), (128, 65), (200, 9), (300, 300)])
+TRSM_SHAPES = [(1, 3), (4, 5), (7, 2), (33, 70), (64, 64), (65, 1), (128, 65), (200, 9), (300, 300)]
+
+
+# (fp64 cases keep their ids; fp32 runs the same shapes under the same relative bound in its own eps)
+@pytest.mark.parametrize("n,k,dtype", [pytest.param(n, k, np.float64, id=f"{n}-{k}") for n, k in TRSM_SHAPES] +
+                         [pytest.param(n, k, np.float32, id=f"{n}-{k}-float32") for n, k in TRSM_SHAPES])
 @pytest.mark.parametrize("upper", [False, True])
 @pytest.mark.parametrize("unit", [False, True])
 @pytest.mark.parametrize("order", ["F", "C"])
-def test_trsm(oracle, n, k, upper, unit, order):
+def test_trsm(oracle, n, k, dtype, upper, unit, order):
     F = init_gpu()
     rng = np.random.default_rng(n * 31 + k)
-    t = rnd(rng, n, n) / (n if unit else 1.0) + n * np.eye(n)
-    b = rnd(rng, n, k)
+    t = np.asarray(rnd(rng, n, n) / (n if unit else 1.0) + n * np.eye(n), dtype=dtype, order="F")
+    b = rnd(rng, n, k, dtype)
     dx = to_dev(b, order)
     fn = {(False, False): F.solve_lower_triangular_in_place, (True, False): F.solve_upper_triangular_in_place,
           (False, True): F.solve_unit_lower_triangular_in_place, (True, True): F.solve_unit_upper_triangular_in_place}
@@ -27,7 +32,7 @@ def test_trsm(oracle, n, k, upper, unit, order):
     got = to_host(dx)
     ref = b.copy(order="F")
     oracle.trsm(t, ref, upper=upper, unit=unit)
-    assert np.abs(got - ref).max() <= 64 * n * EPS[np.dtype(np.float64)] * max(1.0, np.abs(ref).max())
+    assert np.abs(got - ref).max() <= 64 * n * EPS[np.dtype(dtype)] * max(1.0, np.abs(ref).max())
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -770,12 +775,14 @@ def test_ldlt_large_property():
     assert err <= 32 * n * 2.3e-16 * a.abs().max().item()
 
 
-def test_llt_lookahead_on_a_view_with_reversed_rows_and_columns(oracle):
+def test_llt_lookahead_on_a_view_with_reversed_rows_and_columns(oracle, monkeypatch):
     """a Cholesky with n >= 2048 (the look-ahead driver, whose merged trailing update asks the GEMM for a tile skip) on a device
     view with NEGATIVE strides: the buffer-addressed loaders cannot express it, gemm_dev splits the merged update into the two
-    plain products of the pointer-addressed kernel instead of refusing"""
+    plain products of the pointer-addressed kernel instead of refusing.  Below 8192 rows the whole matrix is the
+    sequential tail by default; FAER_HIP_LLT_TAIL=0 keeps the look-ahead steps, and the route counter shows the split ran."""
     import ctypes as C
     F = init_gpu()
+    monkeypatch.setenv("FAER_HIP_LLT_TAIL", "0")
     n = 2304
     rng = np.random.default_rng(77)
     a = spd(rng, n)
@@ -783,8 +790,10 @@ def test_llt_lookahead_on_a_view_with_reversed_rows_and_columns(oracle):
     d = to_dev(np.asfortranarray(a[::-1, ::-1]))
     v = F.MatMut(d.data_ptr() + ((n - 1) * d.stride(0) + (n - 1) * d.stride(1)) * 8, n, n, -d.stride(0), -d.stride(1))
     reg = F.LltRegularization()
-    st = F.lib().libfaer_v0_23_llt_factor_in_place_f64(v, reg, F.PAR_SEQ, F.MemAlloc(), F.lib().libfaer_v0_23_LltParams_f64())
+    with Routes(F) as rt:
+        st = F.lib().libfaer_v0_23_llt_factor_in_place_f64(v, reg, F.PAR_SEQ, F.MemAlloc(), F.lib().libfaer_v0_23_LltParams_f64())
     assert st.tag == 0
+    rt.assert_hit("GemmTriSkipSplit")
     got = to_host(d)[::-1, ::-1]
     ref = a.copy(order="F")
     assert oracle.llt_in_place(ref) == ("ok", 0)

@@ -179,6 +179,27 @@ def test_triangular_matmul(oracle, cs, as_):
             assert np.abs(got - full)[mk].max(initial=0) < 1e-10
 
 
+@pytest.mark.parametrize("cs", STRUCTS)
+def test_triangular_matmul_fp32_float_data(cs):
+    """fp32 float data at n = 700 through every structure triple: integer data cannot see a kernel that accumulates in too
+    little precision, this can -- 4 K eps (|alpha| |A||B| + |C0|) on the structured part, the rest of dst untouched"""
+    F = init_gpu()
+    n, alpha = 700, -0.75
+    rng = np.random.default_rng(700 + STRUCTS.index(cs))
+    mk = mask_of(n, cs)
+    for as_ in STRUCTS:
+        for bs_ in STRUCTS:
+            a, b, c0 = rnd(rng, n, n, np.float32), rnd(rng, n, n, np.float32), rnd(rng, n, n, np.float32)
+            dc = to_dev(c0)
+            F.matmul_triangular(dc, cs, F.ACCUM_ADD, to_dev(a), as_, to_dev(b), bs_, alpha)
+            got = to_host(dc)
+            da, db = dense_of(a.astype(np.float64), as_), dense_of(b.astype(np.float64), bs_)
+            full = c0.astype(np.float64) + alpha * (da @ db)
+            tol = bound(da, db, c0, n, np.float32, alpha)
+            assert (np.abs(got.astype(np.float64) - full)[mk] <= tol[mk]).all(), (cs, as_, bs_)
+            assert np.array_equal(got[~mk], c0[~mk]), (cs, as_, bs_)
+
+
 @pytest.mark.parametrize("kind", ["lower", "upper"])
 @pytest.mark.parametrize("n,k", [(100, 37), (257, 128), (1000, 64)])
 def test_gemm_inner_boundary_dst_kind(kind, n, k):
