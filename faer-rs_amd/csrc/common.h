@@ -343,7 +343,7 @@ template <typename T> void zero_then_upper_dev(MatV<T> out, const MatV<const T> 
 // fplu.hip: LU with full pivoting (perm arrays are host memory); returns the transposition count
 void fplu_debug_inplace(int on); // fplu.hip: 1 = the in-place two-launch path (A/B tests)
 template <typename T> long full_piv_lu_dev(MatV<T> A, idx_t *row_perm, idx_t *row_perm_inv, idx_t *col_perm, idx_t *col_perm_inv);
-// qr.hip: QR with column pivoting (perm arrays are host memory); returns the transposition count
+// colpiv_qr.hip: QR with column pivoting (perm arrays are host memory); returns the transposition count
 template <typename T> long colpiv_qr_dev(MatV<T> A, MatV<T> H, idx_t *col_perm, idx_t *col_perm_inv);
 // pure host planning logic, exported for the CPU tests (faer_hip_debug_*)
 std::vector<idx_t> llt_plan(idx_t n, idx_t tail_rows, idx_t nb2);
@@ -404,11 +404,22 @@ template <typename T> void laswp_list_rows_dev(MatV<T> B, const int *list_4nt, i
 
 // Householder QR without pivoting (qr.hip); H is block_size x min(m,n) (device). returns rank
 template <typename T> long geqrf_dev(MatV<T> A, MatV<T> H, idx_t blocking_threshold);
-// evd/tridiag.rs:274: A (self-adjoint, lower triangle used) -> T + reflectors, H: block Householder factors (qr.hip)
+// the T blocks of H (block_size x min(m, n)) over the first `rank` reflectors of A from their taus (device), the columns from `rank` on
+// in the reference's zero / +inf pattern (qr.hip); the last step of every Householder-based driver
+template <typename T> void qr_t_blocks_from_taus(MatV<T> A, MatV<T> H, idx_t rank, const T *taus);
+// The one-pass QR path (tsqr.hip; float: fused schedule, double: plain schedule) for whole tall matrices (geqrf_dev) and for single
+// panels / two-panel nodes of the classic recursion (qr_rec).  tsqr_factor returns the number of COLUMNS completed, `reason` says
+// why it stopped early; `rows_above`: rows of a parent matrix above A that count in the reference's rank test.
+template <typename T> bool tsqr_applicable(MatV<T> A, idx_t bs);
+template <typename T> bool tsqr_panel_applicable(idx_t m, idx_t w, idx_t rs, idx_t cs);
+template <typename T> idx_t tsqr_factor(MatV<T> A, MatV<T> H, T *taus, int *reason, idx_t rows_above = 0);
+template <> idx_t tsqr_factor<float>(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t rows_above);
+template <> idx_t tsqr_factor<double>(MatV<double> A, MatV<double> H, double *taus, int *reason, idx_t rows_above);
+// evd/tridiag.rs:274: A (self-adjoint, lower triangle used) -> T + reflectors, H: block Householder factors (condense.hip)
 template <typename T> void tridiag_dev(MatV<T> A, MatV<T> H);
-// svd/bidiag.rs:47: A -> upper bidiagonal + reflectors, Hl / Hr: block Householder factors (qr.hip)
+// svd/bidiag.rs:47: A -> upper bidiagonal + reflectors, Hl / Hr: block Householder factors (condense.hip)
 template <typename T> void bidiag_dev(MatV<T> A, MatV<T> Hl, MatV<T> Hr);
-// evd/hessenberg.rs:549: A -> upper Hessenberg + reflectors, H: block Householder factors (qr.hip)
+// evd/hessenberg.rs:549: A -> upper Hessenberg + reflectors, H: block Householder factors (condense.hip)
 template <typename T> void hessenberg_dev(MatV<T> A, MatV<T> H);
 template <typename T>
 void apply_householder_sequence_left_dev(MatV<const T> V, MatV<const T> H, MatV<T> M, bool transpose);

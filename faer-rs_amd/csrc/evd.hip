@@ -1,7 +1,7 @@
 // Self-adjoint eigendecomposition -- faer/src/linalg/evd/mod.rs:270-425 (self_adjoint_evd) with the divide and
 // conquer solver of the symmetric tridiagonal problem, evd/tridiag_evd.rs:270-660, on the device.
 //
-//   copy lower(A) -> tridiag_dev (qr.hip) -> diag / offdiag -> tridiagonal solve -> block Householder back-transform
+//   copy lower(A) -> tridiag_dev (condense.hip) -> diag / offdiag -> tridiagonal solve -> block Householder back-transform
 //   (apply_householder_sequence_left_dev) -> S.
 //
 // The tridiagonal solve follows the reference's recursion (split at n / 2, rank-one tear d[n1-1] -= |rho|, d[n1] -= |rho|)

@@ -1,6 +1,6 @@
 // One-pass tall-skinny Householder QR for gfx950 (fp32 data; fp64 data: the section "fp64 data" further down): faer's (V, T, R) -- qr/no_pivoting/factor.rs:137-256,
 // householder.rs:21-23,59-107,132-272 -- without a cross-workgroup reduction per column.
-// Callers (qr.hip): geqrf_dev for whole matrices of >= 1024 rows and >= 3 rows per column (tsqr_applicable / tsqr_applicable64), and the
+// Callers (qr.hip): geqrf_dev for whole matrices of >= 1024 rows and >= 3 rows per column (tsqr_applicable), and the
 // classic path's recursion for single panels and two-panel nodes of any matrix (tsqr_panel_applicable, `rows_above`).
 //
 // The classic path (qr.hip) follows the reference's recursion: every column of a panel costs one device-wide
@@ -36,6 +36,7 @@
 // NOT exact, R~ is good to ~cond(panel)^2 eps64, so its guard keeps well-conditioned panels only (TqLim<double>::cond_max) and the
 // classic path takes every other one.
 #include <atomic>
+#include <limits>
 
 #include "common.h"
 #include "mfma.h"
@@ -2686,16 +2687,46 @@ void tsqr_debug_shape_rule(long min_rows, long min_aspect)
 	g_tq_min_aspect.store(min_aspect > 0 ? min_aspect : 3);
 }
 
-bool tsqr_applicable(idx_t m, idx_t n, idx_t rs, idx_t cs, idx_t bs)
+static std::atomic<int> g_tq_f64{1};
+void tsqr_debug_f64(int on) { g_tq_f64.store(on); }
+static std::atomic<int> g_tq_panels{1};
+void tsqr_debug_panels(int on) { g_tq_panels.store(on); }
+
+template <typename T> bool tsqr_applicable(MatV<T> A, idx_t bs)
 {
-	if (rs != 1 || cs < m || n < 1 || n > 512 || m < g_tq_min_rows.load() || m < g_tq_min_aspect.load() * n || m >= (1L << 30))
+	const idx_t m = A.nrows, n = A.ncols;
+	if (sizeof(T) == 8 && g_tq_f64.load() == 0)
+		return false;
+	// (columns that are not 16-byte aligned run the scalar-access variants of the streaming kernels)
+	if (A.rs != 1 || A.cs < m || n < 1 || n > 512 || m < g_tq_min_rows.load() || m < g_tq_min_aspect.load() * n || m >= (1L << 30))
 		return false;
 	// T blocks are written per 64-column panel: a block of Q_coeff is either a whole number of panels or divides one
 	return bs % TQ_PW == 0 || TQ_PW % bs == 0;
 }
+template bool tsqr_applicable<float>(MatV<float>, idx_t);
+template bool tsqr_applicable<double>(MatV<double>, idx_t);
+
+// Panels of the classic path (qr.hip, qr_rec): ONE panel of 16 .. 64 columns of a matrix of
+// any shape, rows from its diagonal down, with its w x w block of T.  The one-pass panel costs a fixed ~180 us (Gram launch, reduce,
+// the single-workgroup panel kernel, V launch, status read-back) against 9 us per column of the cooperative leaf + the level-3 steps
+// of the recursion between 8 and 64 columns.
+template <typename T> bool tsqr_panel_applicable(idx_t m, idx_t w, idx_t rs, idx_t cs)
+{
+	if (g_tq_panels.load() == 0 || (sizeof(T) == 8 && g_tq_f64.load() == 0))
+		return false;
+	// (ONE panel: any width up to 64 -- the block-size rule of tsqr_applicable is about panels that share a block of Q_coeff)
+	// (... or a node of exactly two panels, 128 columns -- faer's block size of Q_coeff from N = 4096 on: one call, one read-back, the
+	// first panel applied to the second by the path's own update launch, T12 from its small matrices)
+	if (rs != 1 || cs < m || w < 16 || (w > TQ_PW && w != 2 * TQ_PW) || m < 256 || m < 4 * w || m >= (1L << 30))
+		return false;
+	// (the reference's rank test rejects every column of so tall a matrix: geqrf_classic, ref_rejects_all)
+	return !(16.0 * (double) std::numeric_limits<T>::epsilon() * (double) m >= 1.0);
+}
+template bool tsqr_panel_applicable<float>(idx_t, idx_t, idx_t, idx_t);
+template bool tsqr_panel_applicable<double>(idx_t, idx_t, idx_t, idx_t);
 
 // ------------------------------------------------------------------------------------------------
-// One call of either driver (tsqr_factor: fp32 data, fused schedule; tsqr_factor64: fp64 data, plain schedule): the workspace, the
+// One call of either driver (tsqr_factor<float>: fused schedule; tsqr_factor<double>: plain schedule): the workspace, the
 // launches in front of the first panel, the panel / y / cross-panel T launches and the status read-back.  The schedules stay in the drivers.
 // ------------------------------------------------------------------------------------------------
 template <typename T> struct TqWork {
@@ -2722,7 +2753,7 @@ template <typename T> struct TqWork {
 	// columns the first step's Gram launches do not cover
 	TqWork(MatV<T> A_, MatV<T> H_, T *taus_, idx_t rows_above) : A(A_), H(H_), taus(taus_)
 	{
-		// (the streaming kernels load down the columns: tsqr_applicable / tsqr_applicable64 / tsqr_panel_applicable admit nothing else)
+		// (the streaming kernels load down the columns: tsqr_applicable / tsqr_panel_applicable admit nothing else)
 		FH_CHECK(A.rs == 1, "tsqr: unit row stride");
 		G = small.as<double>();
 		N1 = G + (size_t) TQ_NG * 4096, N3 = N1 + 4096, Gf = N3 + 4096, C = Gf + 4096;
@@ -2890,7 +2921,7 @@ template <typename T> struct TqWork {
 // completed (a multiple of 64, or n); the state is then that of the reference algorithm after those columns: R and
 // V in place, the T blocks in H, taus[j] = T_jj, every reflector applied to all columns on the right.
 // `reason` reports why it stopped early (TQ_FAIL_*).
-idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t rows_above)
+template <> idx_t tsqr_factor<float>(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t rows_above)
 {
 	const TqWork<float> q(A, H, taus, rows_above);
 	const idx_t m = q.m, n = q.n, ld = q.ld;
@@ -3088,42 +3119,8 @@ idx_t tsqr_factor(MatV<float> A, MatV<float> H, float *taus, int *reason, idx_t 
 // ------------------------------------------------------------------------------------------------
 // fp64 driver: the contract of tsqr_factor for double data (columns completed, state of the reference algorithm at that column)
 // ------------------------------------------------------------------------------------------------
-static std::atomic<int> g_tq_f64{1};
-void tsqr_debug_f64(int on) { g_tq_f64.store(on); }
-static std::atomic<int> g_tq_panels{1};
-void tsqr_debug_panels(int on) { g_tq_panels.store(on); }
-
-// Panels of the classic path (qr.hip, qr_rec): ONE panel of 16 .. 64 columns of a matrix of
-// any shape, rows from its diagonal down, with its w x w block of T.  The one-pass panel costs a fixed ~180 us (Gram launch, reduce,
-// the single-workgroup panel kernel, V launch, status read-back) against 9 us per column of the cooperative leaf + the level-3 steps
-// of the recursion between 8 and 64 columns.
-bool tsqr_panel_applicable(idx_t m, idx_t w, idx_t rs, idx_t cs, const void *p, int elem)
-{
-	if (g_tq_panels.load() == 0 || (elem == 8 && g_tq_f64.load() == 0))
-		return false;
-	// (ONE panel: any width up to 64 -- the block-size rule of tsqr_applicable is about panels that share a block of Q_coeff)
-	// (... or a node of exactly two panels, 128 columns -- faer's block size of Q_coeff from N = 4096 on: one call, one read-back, the
-	// first panel applied to the second by the path's own update launch, T12 from its small matrices)
-	if (rs != 1 || cs < m || w < 16 || (w > TQ_PW && w != 2 * TQ_PW) || m < 256 || m < 4 * w || m >= (1L << 30))
-		return false;
-	(void) p;
-	if (elem == 4 && 16.0 * 1.1920928955078125e-07 * (double) m >= 1.0)
-		return false;
-	return true;
-}
-
-bool tsqr_applicable64(idx_t m, idx_t n, idx_t rs, idx_t cs, idx_t bs, const void *p)
-{
-	if (g_tq_f64.load() == 0)
-		return false;
-	if (rs != 1 || cs < m || n < 1 || n > 512 || m < g_tq_min_rows.load() || m < g_tq_min_aspect.load() * n || m >= (1L << 30))
-		return false;
-	(void) p; // (columns that are not 16-byte aligned run the scalar-access variants of the streaming kernels)
-	return bs % TQ_PW == 0 || TQ_PW % bs == 0;
-}
-
 // the plain schedule: Gram, panel, y, update per panel on one stream
-idx_t tsqr_factor64(MatV<double> A, MatV<double> H, double *taus, int *reason, idx_t rows_above)
+template <> idx_t tsqr_factor<double>(MatV<double> A, MatV<double> H, double *taus, int *reason, idx_t rows_above)
 {
 	const TqWork<double> q(A, H, taus, rows_above);
 	const idx_t m = q.m, n = q.n, ld = q.ld;

@@ -30,6 +30,14 @@ static __device__ __forceinline__ double xwg_load(const double *p)
 	return __longlong_as_double((long long) __hip_atomic_load(reinterpret_cast<const xwg_u64 *>(p), __ATOMIC_RELAXED,
 								 __HIP_MEMORY_SCOPE_AGENT));
 }
+static __device__ __forceinline__ void xwg_store(float *p, float v)
+{
+	__hip_atomic_store(reinterpret_cast<int *>(p), __float_as_int(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+static __device__ __forceinline__ float xwg_load(const float *p)
+{
+	return __int_as_float(__hip_atomic_load(reinterpret_cast<const int *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
 static __device__ __forceinline__ void xwg_store_i(int *p, int v)
 {
 	__hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

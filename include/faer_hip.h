@@ -386,7 +386,7 @@ FAER_HIP_API void libfaer_v0_23_full_piv_lu_solve_transpose_in_place_u64_f32(Fae
 /* ---------------------------------------------------------------------------------------------
  * 2d. QR with column pivoting (faer-ffi/src/lib.rs:1721-1876; qr/col_pivoting/factor.rs, solve.rs): HBM-bound;
  *     delayed rank-1 updates fused with the next step's dot products, down-dated column norms with the reference's
- *     recomputation rule (csrc/qr.hip, colpiv_qr_dev).  Permutation slices are HOST memory (ncols entries).
+ *     recomputation rule (csrc/colpiv_qr.hip, colpiv_qr_dev).  Permutation slices are HOST memory (ncols entries).
  * --------------------------------------------------------------------------------------------- */
 FAER_HIP_API FaerColPivQrParams libfaer_v0_23_ColPivQrParams_f64(void);
 FAER_HIP_API FaerLayout libfaer_v0_23_colpiv_qr_factor_in_place_scratch_u32_f64(size_t nrows, size_t ncols, size_t block_size, FaerPar par, FaerColPivQrParams params);
@@ -460,7 +460,7 @@ FAER_HIP_API void libfaer_v0_23_colpiv_qr_inverse_u64_f32(FaerMatMut A_inv, Faer
  * 2e. Self-adjoint eigendecomposition (faer-ffi/src/lib.rs:2368-2400; evd/mod.rs:270-425): A = U diag(S) U^H.
  *     A (n x n): only its lower triangle is read, A is never written.  S (n entries) receives the eigenvalues in
  *     ascending order.  U.ncols == 0: no eigenvectors; otherwise U is n x n and column j is the unit eigenvector of
- *     S[j].  Tridiagonalization (csrc/qr.hip), divide and conquer on the tridiagonal with QR-iteration leaves
+ *     S[j].  Tridiagonalization (csrc/condense.hip), divide and conquer on the tridiagonal with QR-iteration leaves
  *     (csrc/evd.hip), block Householder back-transform.  Leaves hold at most min(max(recursion_threshold, 4), 64) rows:
  *     a larger threshold is clamped to 64 (the decomposition is the same up to rounding).  par, mem and
  *     params.tridiag are accepted and ignored.  NoConvergence: a non-finite entry in the tridiagonal form, or a leaf
@@ -704,7 +704,7 @@ FAER_HIP_API FaerLltStatus faer_hip_dist_llt_f32(FaerMatMut A_local, size_t n_gl
  * tridiagonal T with A = Q T Q^H, the essential parts of the Householder reflectors sit below the subdiagonal and
  * `householder` (block_size x (n - 1), block_size >= 1) holds the block Householder factors of
  * A.submatrix(1, 0, n - 1, n - 1) -- what apply_block_householder_sequence_* consumes (tridiag.rs:516-533, :561-585).
- * Level-2, HBM-bound like the reference (csrc/qr.hip, "Tridiagonalization").  Host or device operands. */
+ * Level-2, HBM-bound like the reference (csrc/condense.hip, "Tridiagonalization").  Host or device operands. */
 FAER_HIP_API void faer_hip_tridiag_in_place_f64(FaerMatMut A, FaerMatMut householder);
 FAER_HIP_API void faer_hip_tridiag_in_place_f32(FaerMatMut A, FaerMatMut householder);
 
@@ -714,7 +714,7 @@ FAER_HIP_API void faer_hip_tridiag_in_place_f32(FaerMatMut A, FaerMatMut househo
  * their block factors in H_right (br x (min(m, n) - 1)) -- the layout apply_block_householder_sequence_* consumes
  * (bidiag.rs:216-254, :404-428).  The reference's SVD only calls it with nrows >= ncols; a wide matrix is processed the
  * way the reference processes it (min(m, n) columns, the last row left normalised without a right reflector).
- * Level-2, HBM-bound like the reference (csrc/qr.hip, "Bidiagonalization").  Host or device operands. */
+ * Level-2, HBM-bound like the reference (csrc/condense.hip, "Bidiagonalization").  Host or device operands. */
 FAER_HIP_API void faer_hip_bidiag_in_place_f64(FaerMatMut A, FaerMatMut H_left, FaerMatMut H_right);
 FAER_HIP_API void faer_hip_bidiag_in_place_f32(FaerMatMut A, FaerMatMut H_left, FaerMatMut H_right);
 
@@ -723,7 +723,7 @@ FAER_HIP_API void faer_hip_bidiag_in_place_f32(FaerMatMut A, FaerMatMut H_left, 
  * A = Q H Q^H, the essential parts of the reflectors sit below the subdiagonal, `householder` (block_size x (n - 1)) holds
  * the block Householder factors of A.submatrix(1, 0, n - 1, n - 1) (hessenberg.rs:382-406, :758-783).  The reference picks
  * an unblocked variant below n = 256 and a blocked one above; both compute the same reflectors in different orders of
- * operations and this entry point agrees with either up to rounding (csrc/qr.hip, "Hessenberg reduction").  Level-2,
+ * operations and this entry point agrees with either up to rounding (csrc/condense.hip, "Hessenberg reduction").  Level-2,
  * HBM-bound.  Host or device operands. */
 FAER_HIP_API void faer_hip_hessenberg_in_place_f64(FaerMatMut A, FaerMatMut householder);
 FAER_HIP_API void faer_hip_hessenberg_in_place_f32(FaerMatMut A, FaerMatMut householder);

@@ -1,4 +1,4 @@
-"""-m gpu parity tests of faer_hip_bidiag_in_place (csrc/qr.hip, "Bidiagonalization") against the CPU oracle's
+"""-m gpu parity tests of faer_hip_bidiag_in_place (csrc/condense.hip, "Bidiagonalization") against the CPU oracle's
 restatement of faer/src/linalg/svd/bidiag.rs:47-255 and the reference's own property test (bidiag.rs:380-440)."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""-m gpu parity tests of faer_hip_hessenberg_in_place (csrc/qr.hip, "Hessenberg reduction") against the CPU oracle's
+"""-m gpu parity tests of faer_hip_hessenberg_in_place (csrc/condense.hip, "Hessenberg reduction") against the CPU oracle's
 restatement of faer/src/linalg/evd/hessenberg.rs:230-408 and the reference's own property test (hessenberg.rs:740-793)."""
 import numpy as np
 import pytest

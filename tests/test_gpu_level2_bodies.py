@@ -1,4 +1,4 @@
-"""-m gpu: the single-workgroup vector kernels of the three reductions to condensed form exist twice (csrc/qr.hip): a body that keeps the
+"""-m gpu: the single-workgroup vector kernels of the three reductions to condensed form exist twice (csrc/condense.hip): a body that keeps the
 columns / rows it touches in registers (at most 4096 remaining rows: every size the other GPU tests reach) and the memory-resident body that
 takes over above.  faer_hip_debug_level2_force_memory_bodies(1) runs the second one at every size: both restate the same expressions with
 the same block reductions; the compiler contracts multiply-adds differently in the two bodies, so the outputs agree to rounding (a few

@@ -1,4 +1,4 @@
-"""GPU parity: the one-pass tall-skinny QR path for fp64 data (csrc/tsqr.hip, tsqr_factor64; qr/no_pivoting/factor.rs:137-256,
+"""GPU parity: the one-pass tall-skinny QR path for fp64 data (csrc/tsqr.hip, tsqr_factor<double>; qr/no_pivoting/factor.rs:137-256,
 householder.rs:59-107) through the C-ABI against the CPU oracle.  The path forms its Gram sums in fp64, so it keeps
 well-conditioned panels only (condition guard: cond_2 below ~8) and hands everything else to the classic path panel by panel."""
 import ctypes as C

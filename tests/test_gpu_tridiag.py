@@ -1,4 +1,4 @@
-"""-m gpu parity tests of faer_hip_tridiag_in_place (csrc/qr.hip, "Tridiagonalization") against the CPU oracle's
+"""-m gpu parity tests of faer_hip_tridiag_in_place (csrc/condense.hip, "Tridiagonalization") against the CPU oracle's
 restatement of faer/src/linalg/evd/tridiag.rs:274-535 and the reference's own property test (tridiag.rs:538-600)."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""fp64 tall-skinny QR on the one-pass path (csrc/tsqr.hip, tsqr_factor64) against the classic path and the oracle:
+"""fp64 tall-skinny QR on the one-pass path (csrc/tsqr.hip, tsqr_factor<double>) against the classic path and the oracle:
 per shape the columns the one-pass path completed, the errors of R / V / T against the oracle in fp64 eps (both paths)
 and the times of both paths.  usage: gpu_qr_f64_onepass.py [big]   (big: also 5e5 x 256 with its oracle run, ~1 min of CPU)"""
 import ctypes as C
