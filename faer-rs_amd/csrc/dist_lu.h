@@ -46,7 +46,7 @@ namespace fh {
 // On the owner itself the update of block column k+1 is issued first, on the stream that also takes the REST of update k
 // (an asynchronous backend: its bulk stream, most of the chip), the panel factorization behind it on the panel stream, the
 // rest last: panel k+1 and the rest of update k run concurrently inside the rank, exactly like the two streams of the
-// single-GPU driver (getrf.hip, getrf_lookahead, "mode 1").  Rounds 2-5 ran the update of block column k+1 on the panel
+// single-GPU driver (getrf.hip, LuLookahead, LuBulk::Plain).  Rounds 2-5 ran the update of block column k+1 on the panel
 // stream's 32 CUs in front of the panel: ~1 ms per step on the critical chain (profiles/r05_bench_dryrun_dist_one_rank.json).
 // Two panel buffers alternate; the pivots stay in the backend's memory until the end (no host synchronisation
 // inside the loop).

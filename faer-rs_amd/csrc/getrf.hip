@@ -22,15 +22,18 @@
 //     raises a device error instead of hanging.
 // Row interchanges of the outside columns are NOT applied one transposition at a time: the transposition list is
 // composed into a net row permutation in parallel (each row traces its source backwards through the list) and
-// applied as one gather.  Large matrices run the recursion with look-ahead on two CU-masked streams
-// (getrf_lookahead).
-#include <climits>
-
+// applied as one gather.
+//
+// Host side, bottom up: LuWork (the workspace of one call), getrf_leaf (which of the four leaves), the two updates everything
+// above a leaf is made of -- LuUpdate (interchanges, solve, product) and lu_node_update (the fused 64-column node) --, getrf_rec
+// (the recursion), getrf_panel_flat / getrf_panel (a panel of <= 512 columns), and for large matrices LuLookahead: the
+// right-looking schedule with look-ahead on two CU-masked streams, its step table in lu_plan, its per-step choice in
+// LuLookahead::decide, one method per kind of step.
 #include <atomic>
+#include <climits>
+#include <optional>
 
 #include "common.h"
-#include <optional>
-#include <functional>
 #include "lds_blocks.h"
 #include "mfma.h"
 #include "xwg.h"
@@ -39,7 +42,12 @@
 
 namespace fh {
 
-constexpr int LU_W = 64; // leaf width of the recursion
+// The three widths of this file, all 64 today, and what ties them together:
+constexpr int LU_W = 64;  // leaf width of the recursion (and the widest leaf: sizes the exchange records of getrf_panel2_kernel)
+constexpr int LUN_W = 64; // width of the node kernel's triangle: left width of lu_node64_kernel = rows of its triangular system
+// (LW_W, lu_wpanel.h: lane count of the wave-panel leaf, lane c <-> panel column c)
+static_assert(LU_W == LW_W, "getrf_leaf hands every full-width leaf of the recursion to the wave-panel kernel");
+static_assert(LUN_W == LU_W, "a node update is the update behind ONE leaf: the leaf's columns are the node kernel's triangle");
 
 // ------------------------------------------------------------------------------------------------
 // Register-resident cooperative panel kernel.  Phase timing of its LDS-resident predecessor
@@ -55,8 +63,7 @@ constexpr int LU_W = 64; // leaf width of the recursion
 // ------------------------------------------------------------------------------------------------
 constexpr int LU2_NT = 512;	  // threads per workgroup
 constexpr int LU2_GMAX = 2048;	  // workgroups per panel (rows / (LU2_NT * RPT))
-constexpr int LU_WMAX = 64;	  // widest leaf
-constexpr int LU2_GSLOT = 4 + 2 * LU_WMAX; // granules per producer slot: {row}, {|a| hi}, {|a| lo}, pad, W x {hi, lo}
+constexpr int LU2_GSLOT = 4 + 2 * LU_W; // granules per producer slot: {row}, {|a| hi}, {|a| lo}, pad, W x {hi, lo}
 
 template <typename T> struct Panel2Args {
 	T *P;
@@ -65,7 +72,7 @@ template <typename T> struct Panel2Args {
 	int *piv; // piv[j] = row_base + pivot row
 	int row_base;
 	xwg_u64 *gran;	    // [2][G][LU2_GSLOT] tagged granules
-	xwg_u64 *gran_diag; // [2][2 * LU_WMAX] row J as published by workgroup 0
+	xwg_u64 *gran_diag; // [2][2 * LU_W] row J as published by workgroup 0
 	xwg_u64 epoch_base;
 	int *status;
 };
@@ -177,7 +184,7 @@ static __device__ __forceinline__ bool panel2_step(const Panel2Args<T> &a, T (&x
 			__builtin_amdgcn_wave_barrier();
 			if (G > 1 && lane < W) {
 				const xwg_u64 db = (xwg_u64) __double_as_longlong((double) sh.drow[lane]);
-				xwg_u64 *dg = a.gran_diag + (size_t) q * 2 * LU_WMAX + 2 * lane;
+				xwg_u64 *dg = a.gran_diag + (size_t) q * 2 * LU_W + 2 * lane;
 				xwg_store_gran(dg, tag, (unsigned) (db >> 32));
 				xwg_store_gran(dg + 1, tag, (unsigned) db);
 			}
@@ -222,7 +229,7 @@ static __device__ __forceinline__ bool panel2_step(const Panel2Args<T> &a, T (&x
 			if (ok) {
 				const bool want = lane < W, want_piv = want && p != J;
 				const xwg_u64 *ps = a.gran + ((size_t) q * G + gw) * LU2_GSLOT + 4 + 2 * (lane & (W - 1));
-				const xwg_u64 *ds = a.gran_diag + (size_t) q * 2 * LU_WMAX + 2 * (lane & (W - 1));
+				const xwg_u64 *ds = a.gran_diag + (size_t) q * 2 * LU_W + 2 * (lane & (W - 1));
 				xwg_u64 ph = 0, pl = 0, dh = 0, dl = 0;
 				ok = 0;
 				for (int spin = 0; spin < (1 << 21); ++spin) {
@@ -457,7 +464,6 @@ __global__ void scatter_rows_kernel(T *B, idx_t rs, idx_t cs, int nrows, int nco
 // gathers their sources into LDS and scatters them back -- no global temporary, no separate compose pass.
 constexpr int LASWP_SMALL_NT = 512;
 constexpr int LASWP_CC = 8;
-constexpr int LUN_W_HOST = 64; // (= LUN_W, defined with the node kernel below)
 
 // `top_out` (optional, nt x ncols, column major with pitch nt): receives a copy of the rows 0 .. nt-1 AFTER the interchanges
 // (the fused node update below reads the block it overwrites from there).
@@ -600,7 +606,6 @@ __global__ __launch_bounds__(256) void laswp_small_kernel(T *B, idx_t rs, idx_t 
 //   * product: D' = (A10 A01)^T per 16 x 16 tile (mfma.h: operand a = U[k][c], b = -L[r][k]), so that 16 consecutive lanes
 //     hold 16 consecutive rows of a column: 128-byte accesses in the column-major panel.
 // ------------------------------------------------------------------------------------------------
-constexpr int LUN_W = 64;   // left width = rows of the triangular system
 constexpr int LU_FLAT_MAXW = 512; // widest flat panel / widest run of column groups one node launch serves: sizes LuWork::ttop
 constexpr int LUN_LP = 65;  // LDS pitch of L00 (row major: broadcast reads)
 constexpr int LUN_UP = 80;  // LDS pitch of U (k major; pitch = 16 mod 32 keeps the four k groups of an operand read on disjoint banks)
@@ -890,7 +895,7 @@ template <typename T> static void laswp_dev(MatV<T> B, const int *piv, int nt, i
 	hipStream_t s = ctx().stream;
 	if (nt <= LASWP_SMALL_NT) {
 		hipLaunchKernelGGL(laswp_small_kernel<T>, dim3((unsigned) ((B.ncols + LASWP_CC - 1) / LASWP_CC)), dim3(256), 0, s, B.p,
-				   B.rs, B.cs, nrows, (int) B.ncols, piv, nt, row_base, top_out, (nt == LUN_W_HOST && top_out) ? L00 : (const T *) nullptr, lcs);
+				   B.rs, B.cs, nrows, (int) B.ncols, piv, nt, row_base, top_out, (nt == LUN_W && top_out) ? L00 : (const T *) nullptr, lcs);
 		FH_HIP(hipGetLastError());
 		return;
 	}
@@ -915,16 +920,38 @@ template <typename T> static void laswp_dev(MatV<T> B, const int *piv, int nt, i
 // ------------------------------------------------------------------------------------------------
 // driver
 // ------------------------------------------------------------------------------------------------
+// The workspace of one factorization (getrf_dev) or one panel (getrf_panel_dev), on the stream of the call.  The buffers are
+// released on return while the launches may still be queued: the pool hands a buffer back to the SAME stream only.
 template <typename T> struct LuWork {
-	int *piv;	    // device, min(m, n) entries, absolute rows
-	xwg_u64 *gran;	    // [LU2_NSLOT][LU2_GMAX][LU2_GSLOT] tagged granules (zeroed once per factorization)
-	xwg_u64 *gran_diag; // [LU2_NSLOT][2 * LU_W]
-	xwg_u64 epoch_base; // epochs consumed by earlier leaf launches of this factorization
-	unsigned char *wws = nullptr; // LW_WS_BYTES of getrf_wpanel_kernel's exchange records (zeroed once per factorization)
-	T *ttop = nullptr;	      // LUN_W x LU_FLAT_MAXW scalars: the interchanged top blocks (64 x 64 each, one per 64-column group right of a leaf)
-				      // that lu_node64_kernel reads -- up to LU_FLAT_MAXW / 64 - 1 groups from a flat panel or a staged last leaf
-	int *status;
-	bool general = false;		 // every leaf on the non-cooperative path (rerun after an exchange timeout, debug switch)
+	static constexpr size_t GRAN_BYTES = (size_t) LU2_NSLOT * LU2_GMAX * LU2_GSLOT * sizeof(xwg_u64);
+	static constexpr size_t DIAG_BYTES = (size_t) LU2_NSLOT * 2 * LU_W * sizeof(xwg_u64);
+	Scratch granb{GRAN_BYTES + DIAG_BYTES};
+	Scratch misc{256};
+	Scratch wwsb{LW_WS_BYTES};
+	Scratch ttopb{(size_t) LUN_W * LU_FLAT_MAXW * sizeof(T)};
+	std::optional<Scratch> pivb; // (unless the caller brings the pivot array)
+	int *piv;					    // device, `size` entries, absolute rows
+	xwg_u64 *gran = granb.as<xwg_u64>();		    // [LU2_NSLOT][LU2_GMAX][LU2_GSLOT] tagged granules (zeroed once per factorization)
+	xwg_u64 *gran_diag = gran + GRAN_BYTES / sizeof(xwg_u64); // [LU2_NSLOT][2 * LU_W]
+	xwg_u64 epoch_base = 0;				    // epochs consumed by earlier leaf launches of this factorization
+	unsigned char *wws = wwsb.as<unsigned char>();	    // LW_WS_BYTES of getrf_wpanel_kernel's exchange records (zeroed once per factorization)
+	T *ttop = ttopb.as<T>(); // LUN_W x LU_FLAT_MAXW scalars: the interchanged top blocks (64 x 64 each, one per 64-column group right of a leaf)
+				 // that lu_node64_kernel reads -- up to LU_FLAT_MAXW / 64 groups behind a staged last leaf (lu_node_update)
+	int *status;		 // word 2: an exchange timed out
+	bool general = false;	 // every leaf on the non-cooperative path (rerun after an exchange timeout, debug switch)
+
+	// `piv_dev` / `status_dev` (device; status_dev: 16 zeroed ints): the caller's, or nullptr: the workspace's own
+	LuWork(idx_t size, int *piv_dev, int *status_dev)
+	{
+		if (!piv_dev)
+			pivb.emplace((size_t) size * sizeof(int));
+		piv = piv_dev ? piv_dev : pivb->as<int>();
+		status = status_dev ? status_dev : misc.as<int>() + 8;
+		FH_HIP(hipMemsetAsync(wwsb.p, 0, LW_WS_BYTES, ctx().stream));
+		clear_status();
+		FH_HIP(hipMemsetAsync(granb.p, 0, GRAN_BYTES + DIAG_BYTES, ctx().stream));
+	}
+	void clear_status() { FH_HIP(hipMemsetAsync(misc.p, 0, 256, ctx().stream)); } // (the workspace's own block)
 };
 
 // rows per workgroup of the cooperative kernel for a leaf of w columns (registers: RPT x W scalars per thread)
@@ -1092,7 +1119,7 @@ template <typename T> __global__ __launch_bounds__(256) void lug_pivot_kernel(co
 
 template <typename T> __global__ __launch_bounds__(256) void lug_update_kernel(const LugArgs<T> a)
 {
-	__shared__ T su[LU_WMAX];
+	__shared__ T su[LU_W];
 	const int tid = threadIdx.x;
 	if (tid < a.w)
 		su[tid] = a.urow[tid];
@@ -1111,7 +1138,7 @@ template <typename T> static void getrf_leaf_general(MatV<T> P, int col0, int ro
 {
 	const idx_t m = P.nrows;
 	const int w = (int) P.ncols;
-	FH_CHECK(w <= LU_WMAX, "getrf leaf: panel too wide");
+	FH_CHECK(w <= LU_W, "getrf leaf: panel too wide");
 	hipStream_t s = ctx().stream;
 	int nwg = (int) ((m + 255) / 256);
 	if (nwg > 1024)
@@ -1119,7 +1146,7 @@ template <typename T> static void getrf_leaf_general(MatV<T> P, int col0, int ro
 	if (nwg < 1)
 		nwg = 1;
 	// (released on return while the launches may still be queued: the pool hands a buffer back to the SAME stream only)
-	Scratch pvb((size_t) nwg * sizeof(double)), prb((size_t) nwg * sizeof(int)), ub((size_t) LU_WMAX * sizeof(T));
+	Scratch pvb((size_t) nwg * sizeof(double)), prb((size_t) nwg * sizeof(int)), ub((size_t) LU_W * sizeof(T));
 	LugArgs<T> a;
 	a.P = P.p;
 	a.rs = P.rs;
@@ -1216,7 +1243,7 @@ template <typename T> static void getrf_leaf(MatV<T> P, int col0, int row_base, 
 		FH_HIP(hipGetLastError());
 		return;
 	}
-	if (lw == LU_W && w <= m && wk.wws) {
+	if (lw == LU_W && w <= m) {
 		// round-4 kernel (lu_wpanel.h): one exchange per column.  64 x RPT rows per wavefront; four wavefronts per workgroup
 		// (one per SIMD) while that many workgroups are resident, else eight
 		constexpr int RPT = sizeof(T) == 8 ? 1 : 2;
@@ -1307,10 +1334,71 @@ static idx_t next_pow2(idx_t n)
 	return p;
 }
 
-// P: the panel (all remaining rows x n columns); col0/row_base: absolute position of P(0,0).
+// ------------------------------------------------------------------------------------------------
+// The two updates every driver below is made of.  P: a view whose rows and columns the positions count from; P(0, 0) sits
+// at row `row_base`, column `col0` of the matrix (pivots are absolute rows, wk.piv is indexed by absolute column).
+// ------------------------------------------------------------------------------------------------
+// Block update (factor.rs:98-117) by the pivot block [r0, r0 + qw) of P, on the columns [c0, c0 + nc): the block's row
+// interchanges, U = L_qq^-1 (.), product with the rows below (none: skipped).  `list`: the interchanges composed once
+// (laswp_compose_list) for several ranges, or nullptr: every launch rebuilds them from the pivot array.  A schedule that
+// splits the update over streams or column ranges calls the three parts.
+template <typename T> struct LuUpdate {
+	MatV<T> P;
+	idx_t r0, qw;
+	const int *piv; // the block's pivots
+	int row0;	// absolute row of P(r0, .)
+	const LaswpList *list;
+	void swaps(idx_t c0, idx_t nc) const
+	{
+		MatV<T> B = P.sub(r0, c0, P.nrows - r0, nc);
+		if (list)
+			laswp_list_dev<T>(B, *list);
+		else
+			laswp_dev<T>(B, piv, (int) qw, row0);
+	}
+	void solve(idx_t c0, idx_t nc) const { trsm_lower_dev<T>(P.sub(r0, r0, qw, qw).c(), true, P.sub(r0, c0, qw, nc)); }
+	void product(idx_t c0, idx_t nc) const
+	{
+		const idx_t r1 = r0 + qw;
+		if (P.nrows > r1)
+			gemm_dev<T>(P.sub(r1, c0, P.nrows - r1, nc), DST_FULL, true, P.sub(r1, r0, P.nrows - r1, qw).c(), P.sub(r0, c0, qw, nc).c(), (T) -1);
+	}
+	void operator()(idx_t c0, idx_t nc) const
+	{
+		swaps(c0, nc);
+		solve(c0, nc);
+		product(c0, nc);
+	}
+};
+
+// Fused node update behind the leaf at P(r0, r0) (LUN_W columns) on the `nr` columns right of it: the leaf's interchanges, which
+// also solve and gather the top block into wk.ttop (laswp_small_kernel with L00), then ONE launch of lu_node64_kernel, its
+// 64-column groups along blockIdx.y.  Needs P.rs == 1 and lu_node_offsets_ok.
+// `two_per_cu`: every workgroup solves the 64 x 64 system of its column group before it updates, so with many row chunks and several
+// column groups a workgroup takes several chunks -- two workgroups per compute unit of the stream in all (measured: 2 workgroups per
+// CU 88.1-88.2 ms, 1: 88.7, 3-4: 88.5, one chunk per workgroup 88.9-89.2 -- profiles/r05_exp_lu_driver.txt).  The recursion's
+// 128-column nodes run one chunk per workgroup whatever their height (outside look-ahead they have more than 2 x CUs chunks).
+template <typename T> static void lu_node_update(MatV<T> P, int col0, int row_base, idx_t r0, idx_t nr, LuWork<T> &wk, bool two_per_cu)
+{
+	FH_CHECK(nr <= LU_FLAT_MAXW, "lu: more column groups than LuWork::ttop holds");
+	const idx_t m = P.nrows - r0;
+	T *leaf = P.sub(r0, r0, m, LUN_W).p;
+	laswp_dev<T>(P.sub(r0, r0 + LUN_W, m, nr), wk.piv + col0 + r0, LUN_W, row_base + (int) r0, wk.ttop, (const T *) leaf, P.cs);
+	unsigned nwg = m > LUN_W ? (unsigned) ((m - LUN_W + LUN_ROWS - 1) / LUN_ROWS) : 1u; // chunks of rows below the leaf
+	const unsigned ncg = (unsigned) ((nr + LUN_W - 1) / LUN_W);
+	if (two_per_cu) {
+		const unsigned cap = (unsigned) (2 * ctx().stream_cus()) / ncg;
+		if (nwg > cap)
+			nwg = cap < 1u ? 1u : cap;
+	}
+	hipLaunchKernelGGL(lu_node64_kernel<T>, dim3(nwg, ncg), dim3(256), 0, ctx().stream, leaf, P.cs, (int) m, (int) nr, (const T *) wk.ttop, 1);
+	FH_HIP(hipGetLastError());
+}
+
+// The reference's recursion (factor.rs:68-187).  P: the panel (all remaining rows x n columns, n <= m).
 template <typename T> static void getrf_rec(MatV<T> P, int col0, int row_base, LuWork<T> &wk)
 {
-	const idx_t m = P.nrows, n = P.ncols; // n <= m
+	const idx_t m = P.nrows, n = P.ncols;
 	if (n == 0)
 		return;
 	{
@@ -1327,81 +1415,62 @@ template <typename T> static void getrf_rec(MatV<T> P, int col0, int row_base, L
 	if (pw > 16)
 		pw = 16;
 	const idx_t bs = (half + pw - 1) / pw * pw;
-	MatV<T> left = P.sub(0, 0, m, bs), right = P.sub(0, bs, m, n - bs);
-	getrf_rec<T>(left, col0, row_base, wk);
+	getrf_rec<T>(P.sub(0, 0, m, bs), col0, row_base, wk);
 	// bring the right half up to date: swaps, A01 <- L00^-1 A01, A11 -= A10 A01 (factor.rs:98-117)
-	MatV<T> A00 = P.sub(0, 0, bs, bs), A01 = P.sub(0, bs, bs, n - bs), A10 = P.sub(bs, 0, m - bs, bs),
-		A11 = P.sub(bs, bs, m - bs, n - bs);
-	if (bs == LUN_W && n - bs <= LUN_W && P.rs == 1 && wk.ttop && lu_node_offsets_ok<T>(m, P.cs)) {
-		// the 128-column nodes: interchanges (+ a copy of the interchanged top block), then solve and product in one launch
-		laswp_dev<T>(right, wk.piv + col0, (int) bs, row_base, wk.ttop, (const T *) P.p, P.cs);
-		const idx_t below = m - bs;
-		const unsigned nwg = below > 0 ? (unsigned) ((below + LUN_ROWS - 1) / LUN_ROWS) : 1u;
-		hipLaunchKernelGGL(lu_node64_kernel<T>, dim3(nwg), dim3(256), 0, ctx().stream, P.p, P.cs, (int) m, (int) (n - bs), (const T *) wk.ttop, 1);
-		FH_HIP(hipGetLastError());
-	} else {
-		laswp_dev<T>(right, wk.piv + col0, (int) bs, row_base);
-		trsm_lower_dev<T>(A00.c(), true, A01);
-		gemm_dev<T>(A11, DST_FULL, true, A10.c(), A01.c(), (T) -1);
-	}
-	getrf_rec<T>(A11, col0 + (int) bs, row_base + (int) bs, wk);
+	if (bs == LUN_W && n - bs <= LUN_W && P.rs == 1 && lu_node_offsets_ok<T>(m, P.cs))
+		lu_node_update<T>(P, col0, row_base, 0, n - bs, wk, false); // the 128-column nodes
+	else
+		LuUpdate<T>{P, 0, bs, wk.piv + col0, row_base, nullptr}(bs, n - bs);
+	getrf_rec<T>(P.sub(bs, bs, m - bs, n - bs), col0 + (int) bs, row_base + (int) bs, wk);
 	// the right half's transpositions act on the rows below bs of the left half (factor.rs:127-185)
-	laswp_dev<T>(A10, wk.piv + col0 + bs, (int) (n - bs < m - bs ? n - bs : m - bs), row_base + (int) bs);
+	laswp_dev<T>(P.sub(bs, 0, m - bs, bs), wk.piv + col0 + bs, (int) (n - bs < m - bs ? n - bs : m - bs), row_base + (int) bs);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Flat right-looking panel (round 5): the panels of the look-ahead driver below.  getrf_rec's binary recursion puts, per 512
 // columns, 4 fused 64-column nodes, 2 nodes of 128 (interchanges, substitution leaf, K = 128 product) and one of 256
 // (interchanges, a three-launch solve, K = 256 product) on the panel stream's dependent chain -- every one of them bound by its
-// own latency on the 32 reserved CUs.  Here every 64-column leaf is applied at once to ALL panel columns right of it: one
-// interchange launch + ONE launch of the fused node kernel (its column groups along blockIdx.y), K = 64.  Same operations per
-// entry as the recursion (factor.rs:98-117 with bs = 64 at every level), regrouped; same pivots.
-//   after_leaf(j): called behind leaf j and the interchanges it makes on the panel's earlier columns `cols_from .. 64 j`
-//   (the staged driver starts the bulk stream's work on a finished part there); `left_from(j)`: first panel column leaf j's
-//   interchanges are applied to at once (the staged driver defers the ones that reach into an earlier part).
+// own latency on the 32 reserved CUs.  Here every 64-column leaf is applied at once to ALL panel columns right of it
+// (lu_node_update), K = 64.  Same operations per entry as the recursion (factor.rs:98-117 with bs = 64 at every level),
+// regrouped; same pivots.
+//   The staged driver hands the panel over in two parts: `first` = width of the first part (0: one part).  A leaf's interchanges
+//   on the panel columns to its left stay inside its part, and `first_done()` is called once the first part is final (the bulk
+//   stream's work on it starts there); the second part's interchanges on the first part's columns are left to the caller.
 // ------------------------------------------------------------------------------------------------
 template <typename T> static bool flat_panel_ok(MatV<T> P, const LuWork<T> &wk)
 {
-	return P.rs == 1 && wk.ttop && P.ncols % LUN_W == 0 && P.ncols <= LU_FLAT_MAXW && P.nrows >= P.ncols && lu_node_offsets_ok<T>(P.nrows, P.cs) && !wk.general &&
+	return P.rs == 1 && P.ncols % LUN_W == 0 && P.ncols <= LU_FLAT_MAXW && P.nrows >= P.ncols && lu_node_offsets_ok<T>(P.nrows, P.cs) && !wk.general &&
 	       !g_lu_force_general.load() && leaf_width_for<T>(P.nrows) == LU_W;
 }
-template <typename T, typename LeftFrom, typename AfterLeaf>
-static void getrf_panel_flat(MatV<T> P, int col0, int row_base, LuWork<T> &wk, LeftFrom left_from, AfterLeaf after_leaf)
+template <typename T, typename FirstDone>
+static void getrf_panel_flat(MatV<T> P, int col0, int row_base, LuWork<T> &wk, idx_t first, FirstDone first_done)
 {
 	const idx_t m = P.nrows, w = P.ncols;
-	const idx_t nl = w / LUN_W;
-	for (idx_t j = 0; j < nl; ++j) {
-		const idx_t c = j * LUN_W;
+	for (idx_t c = 0; c < w; c += LUN_W) {
 		getrf_leaf<T>(P.sub(c, c, m - c, LUN_W), col0 + (int) c, row_base + (int) c, wk);
 		// the leaf's transpositions on the panel columns to its left (factor.rs:127-185)
-		const idx_t lf = left_from(j);
+		const idx_t lf = c < first ? 0 : first;
 		if (c > lf)
 			laswp_dev<T>(P.sub(c, lf, m - c, c - lf), wk.piv + col0 + c, (int) LUN_W, row_base + (int) c);
-		after_leaf(j);
-		const idx_t nr = w - c - LUN_W;
-		if (nr > 0) {
-			// ... and on the columns to its right, which then take the leaf's update: A01 <- L00^-1 A01, A11 -= A10 A01
-			FH_CHECK(nr <= LU_FLAT_MAXW - LUN_W, "lu: more column groups than LuWork::ttop holds");
-			laswp_dev<T>(P.sub(c, c + LUN_W, m - c, nr), wk.piv + col0 + c, (int) LUN_W, row_base + (int) c, wk.ttop, (const T *) (P.p + c + c * P.cs), P.cs);
-			const idx_t below = m - c - LUN_W;
-			unsigned nwg = below > 0 ? (unsigned) ((below + LUN_ROWS - 1) / LUN_ROWS) : 1u;
-			const unsigned ncg = (unsigned) ((nr + LUN_W - 1) / LUN_W);
-			// (every workgroup solves the 64 x 64 system of its column group before it updates: with many row chunks and several
-			// column groups a workgroup takes several chunks -- two workgroups per compute unit of the stream in all)
-			// (measured: 2 workgroups per CU 88.1-88.2 ms, 1: 88.7, 3-4: 88.5, one chunk per workgroup 88.9-89.2 -- profiles/r05_exp_lu_driver.txt)
-			const unsigned cap = (unsigned) (2 * ctx().stream_cus()) / ncg;
-			if (nwg > cap)
-				nwg = cap < 1u ? 1u : cap;
-			hipLaunchKernelGGL(lu_node64_kernel<T>, dim3(nwg, ncg), dim3(256), 0, ctx().stream, P.p + c + c * P.cs, P.cs, (int) (m - c), (int) nr,
-					   (const T *) wk.ttop, 1);
-			FH_HIP(hipGetLastError());
-		}
+		if (c + LUN_W == first)
+			first_done();
+		// ... and on the columns to its right, which then take the leaf's update: A01 <- L00^-1 A01, A11 -= A10 A01
+		if (w - c - LUN_W > 0)
+			lu_node_update<T>(P, col0, row_base, c, w - c - LUN_W, wk, true);
 	}
+}
+// one panel on the current stream: flat where its shape allows (a panel of the look-ahead driver: same launches, same pivots), else the recursion
+template <typename T> static void getrf_panel(MatV<T> P, int col0, int row_base, LuWork<T> &wk)
+{
+	if (flat_panel_ok<T>(P, wk))
+		getrf_panel_flat<T>(P, col0, row_base, wk, 0, [] {});
+	else
+		getrf_rec<T>(P, col0, row_base, wk);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Right-looking driver with look-ahead for large matrices (same idea as potrf.hip): steps of LU_LA_NB columns,
-//     [panel stream]  P_k : recursive panel factorization above on the m_k x nb panel (cooperative leaves; <= 16
+//     [panel stream]  P_k : panel factorization above on the m_k x nb panel (cooperative leaves; <= 16
 //                     workgroups for 16384 rows, they fit the CUs reserved for this stream)
 //     [bulk stream]   columns of panel k+1 first: interchanges, U = L_kk^-1 A_k,k+1, A_{>k,k+1} -= L_{>k,k} U
 //                     -> releases P_{k+1} on the panel stream
@@ -1409,342 +1478,338 @@ static void getrf_panel_flat(MatV<T> P, int col0, int row_base, LuWork<T> &wk, L
 //                     columns left of the panel
 // so the chain of per-column pivot exchanges (the serial part of LU) overlaps with the trailing GEMMs.
 // Same operations per entry as the reference's recursion (factor.rs:68-187) regrouped by block columns.
+//   lu_plan            the step table and the pipelined phase's column cut, from the shape and the plan knobs alone
+//   LuLookahead        one call: what the schedule shares (streams, events, the interchange list, how the last panel was handed over)
+//     ::decide         what step k is: one of the bulk-side kinds (LuBulk) and one of the panel forms (LuPanelForm)
+//     ::bulk_* / ::panel_*   one method per kind;  ::run  the step loop: decide, switch, record
 // ------------------------------------------------------------------------------------------------
-constexpr idx_t LU_LA_NB = 512;
+constexpr idx_t LU_LA_NB = 512;	 // step width while the bulk stream is the critical one
+constexpr idx_t LU_LA_NB2 = 256; // ... once the panel chain is
+static_assert(LU_LA_NB <= LASWP_SMALL_NT, "panel interchange list");
 
-template <typename T> static void getrf_lookahead(MatV<T> A, LuWork<T> &wk, hipStream_t caller)
+// Step plan: LU_LA_NB-column panels while the bulk stream is the critical one (wide steps keep its trailing products at
+// K = 512); once the panel chain is critical (fewer than `nb2_from` rows below the panel) the steps narrow to LU_LA_NB2 columns:
+// the top node of a panel's recursion -- interchanges, a solve against half the panel, a product on the reserved CUs -- is
+// then done by the (idle) bulk stream as part of its update, and what sits between two panels is half as long.
+// (measured: profiles/r05_exp_lu_driver.txt -- N = 16384 92.4 -> 90.5 ms, N = 8192 34.0 -> 30.8 ms; a third, 128-column level
+// and other switch-over points change nothing; with the leaf-wise hand-over: switch-over at 12288 / 11264 / 10240 / 9216 / 8192
+// rows: 89.3 / 88.0 / 86.8-86.9 / 86.5-86.6 / 86.8 ms -- 9216)
+struct LuPlan {
+	idx_t n, nb2_from, pipe_from;
+	std::vector<idx_t> J; // step k factors the columns [J[k], J[k + 1])
+	idx_t jA = 0;	      // the pipelined steps cut the columns right of the panel here (LuLookahead::bulk_pipelined)
+	idx_t nsteps() const { return (idx_t) J.size() - 1; }
+	idx_t at(idx_t k) const { return k < (idx_t) J.size() ? J[(size_t) k] : n; }
+	// remaining rows from which the bulk stream is the critical one ("mode 2"); fewer: the panel chain is
+	bool bulk_bound(idx_t rows_below) const { return rows_below >= nb2_from; }
+};
+// (the overrides of faer_hip_debug_lu_plan: 0 = the tuned default)
+static LuPlan lu_plan(idx_t m, idx_t n, long nb2_override, long pipe_override)
 {
-	Ctx &c = ctx();
-	const idx_t m = A.nrows, n = A.ncols; // n <= m
-	// Step plan: LU_LA_NB-column panels while the bulk stream is the critical one (wide steps keep its trailing products at
-	// K = 512); once the panel chain is critical (fewer than `nb2_from` rows below the panel) the steps narrow to `nb2` columns:
-	// the top node of a panel's recursion -- interchanges, a solve against half the panel, a product on the reserved CUs -- is
-	// then done by the (idle) bulk stream as part of its update, and what sits between two panels is half as long.
-	// (measured: profiles/r05_exp_lu_driver.txt -- N = 16384 92.4 -> 90.5 ms, N = 8192 34.0 -> 30.8 ms; a third, 128-column level
-	// and other switch-over points change nothing)
-	// (second half of round 5, with the leaf-wise hand-over: switch-over at 12288 / 11264 / 10240 / 9216 / 8192 rows: 89.3 / 88.0 / 86.8-86.9 /
-	// 86.5-86.6 / 86.8 ms -- 9216, for the bulk_bound threshold below as well)
-	constexpr idx_t LU_LA_NB2 = 256;
-	const idx_t LU_LA_NB2_FROM = g_lu_plan_nb2_from.load() > 0 ? (idx_t) g_lu_plan_nb2_from.load() : 9216;
-	std::vector<idx_t> J;
-	J.push_back(0);
-	while (J.back() < n) {
-		const idx_t j0 = J.back();
-		idx_t w = m - j0 - LU_LA_NB >= LU_LA_NB2_FROM ? LU_LA_NB : LU_LA_NB2;
+	const idx_t nb2_from = nb2_override > 0 ? (idx_t) nb2_override : 9216;
+	const idx_t pipe_from = pipe_override > 0 ? (idx_t) pipe_override : 13312;
+	LuPlan p{n, nb2_from, pipe_from, {0}};
+	while (p.J.back() < n) {
+		const idx_t j0 = p.J.back();
+		idx_t w = m - j0 - LU_LA_NB >= nb2_from ? LU_LA_NB : LU_LA_NB2;
 		if (w > n - j0)
 			w = n - j0;
-		J.push_back(j0 + w);
+		p.J.push_back(j0 + w);
 	}
-	const idx_t nsteps = (idx_t) J.size() - 1;
-	auto Jat = [&](idx_t k) { return k < (idx_t) J.size() ? J[(size_t) k] : n; };
-	c.reset_events();
-	hipEvent_t e0 = c.next_event();
-	FH_HIP(hipEventRecord(e0, caller));
-	stream_wait(c.la_bulk, e0);
-	stream_wait(c.la_panel, e0);
-	hipEvent_t ev_panel;
+	// the boundary: the middle of the columns right of the next panel, taken at the middle step of the pipelined phase
+	idx_t kend = 0;
+	while (kend + 1 < p.nsteps() && m - p.J[(size_t) kend + 1] >= pipe_from - 3072)
+		++kend;
+	p.jA = (p.at(kend / 2 + 2) + n) / 2 / LU_LA_NB * LU_LA_NB;
+	return p;
+}
+
+// How the bulk side brings the columns right of panel k up to date.  Every solve U = L_kk^-1 A is a dependent chain of ~8
+// launches whose length does not depend on the number of columns (profiles/r04_lu_v4_timeline.txt: ~240 us per chain, three
+// chains per step -- the first 64 columns of the next panel, its other 448, the rest -- were 20 of the bulk stream's 87 ms), so
+// the kinds differ in how they group the columns.  Measured in one visit (profiles/r04_exp_lu_chain_grouping.txt, N = 16384):
+// three chains 107.9 ms, Plain everywhere 102.4, OneChain everywhere 101.6, OneChain down to 10240 remaining rows 100.7.
+enum class LuBulk {
+	Pipelined,  // bulk bound, far from the end: all chains on the side stream one product ahead, the bulk stream only multiplies
+	StagedLeaf, // the panel was handed over in two parts (FlatStaged): only its last leaf is left for the next panel's columns
+	StagedHalf, // ... in two halves (RecStaged): its second half is left
+	SideChain,  // bulk bound: the chain of the columns behind the next panel on the side stream, beside the bulk stream's
+	OneChain,   // bulk bound, no side stream or nothing behind the next panel: ONE chain for all columns, two products
+	Plain,	    // panel bound: the next panel's columns first (all of them), then the rest
+	Last	    // no columns right of the panel
+};
+enum class LuPanelForm {
+	Plain,	    // getrf_panel
+	FlatStaged, // flat, handed to the bulk stream in two parts
+	RecStaged   // the recursion's top level written out, handed over in two halves (shapes flat_panel_ok refuses)
+};
+
+template <typename T> struct LuLookahead {
+	MatV<T> A;
+	LuWork<T> &wk;
+	hipStream_t caller;
+	Ctx &c = ctx();
+	const idx_t m = A.nrows, n = A.ncols; // n <= m
+	const LuPlan plan = lu_plan(m, n, g_lu_plan_nb2_from.load(), g_lu_plan_pipe_from.load());
+	hipStream_t side = nullptr;
 	// net row permutation of a panel's interchanges, composed once (laswp_compose_list_kernel) and shared by all the interchange
-	// launches for it.  Round 4: composed on the BULK stream at the start of the step that applies it (22 us that used to sit
-	// on the panel stream's chain).
-	static_assert(LU_LA_NB <= LASWP_SMALL_NT, "panel interchange list");
-	// (a ring of lists: in the pipelined steps below the side stream composes step k + 1's list while the bulk stream still
-	// applies step k's to the columns left of the panel)
-	constexpr idx_t NLIST = 4;
-	Scratch listb((size_t) NLIST * 2 * 2 * LU_LA_NB * sizeof(int));
+	// launches for it, on the BULK side at the start of the step that applies it (22 us that used to sit on the panel stream's
+	// chain).  A ring of lists: in the pipelined steps the side stream composes step k + 1's list while the bulk stream still
+	// applies step k's to the columns left of the panel.
+	static constexpr idx_t NLIST = 4;
+	Scratch listb{(size_t) NLIST * 2 * 2 * LU_LA_NB * sizeof(int)};
 	LaswpList full;
-	auto use_list = [&](idx_t k) {
-		full.dst = listb.as<int>() + (size_t) (k % NLIST) * 4 * LU_LA_NB;
-		full.src = full.dst + 2 * LU_LA_NB;
+	hipEvent_t ev_panel = nullptr;				// panel k is final (panel stream)
+	hipEvent_t ev_next = nullptr;				// the columns of panel k + 1 are up to date with panel k
+	hipEvent_t ev_GA_prev = nullptr, ev_GB_prev = nullptr;	// the previous step's products on the two column groups (bulk stream)
+	hipEvent_t ev_stage[2] = {nullptr, nullptr};		// stage q of the panel being staged is done (bulk stream)
+	// how panel k was handed over: staged = it has already been applied to the next panel's columns except for its last part
+	LuPanelForm handed = LuPanelForm::Plain;
+	LuUpdate<T> u{}; // the update by panel k; its interchanges come from `full`: valid once compose() has run in this step
+
+	struct Step {
+		idx_t j0, j1, j2, w, w2, w3; // panel k = [j0, j1), w columns; the next two: w2 from j1, w3 from j2
+		LuBulk bulk;
+		LuPanelForm panel; // (of the next panel; Plain if there is none)
 	};
-	use_list(0);
-	// Pipelined steps (while the bulk stream is the critical one).  Between two trailing products the bulk stream used to run
-	// the chain "interchanges, solve, product" for the next panel's columns (~0.3 ms busy) and then wait for the side stream's
-	// chain on the far columns (~0.25 ms idle): ~0.55 ms per step in which most of the chip does nothing.  The columns right of
-	// the panel are now cut at a fixed column jA into a near group A (with the next panel's columns) and a far group B, and ALL
-	// chains run on the side stream one product ahead: the chain of step k + 1 on A runs beside the product of step k on B, the
-	// chain on B beside the product of step k + 1 on A.  The bulk stream issues nothing but the two products per step.
-	// It pays while a product is much longer than a chain: down to 13312 rows below the panel (N = 16384: the first six steps;
-	// 89.7-90.1 -> 88.2-88.5 ms; down to 10240 rows 89.0 -- later the chains, which run 2-4 x slower among a product's workgroups,
-	// no longer fit beside half a product: profiles/r05_exp_lu_driver.txt).
-	const idx_t LU_PIPE_FROM = g_lu_plan_pipe_from.load() > 0 ? (idx_t) g_lu_plan_pipe_from.load() : 13312;
-	idx_t jA = 0;
+
+	// What step k is.  Reads the plan, how panel k was handed over (`handed`) and whether the side stream exists.
+	Step decide(idx_t k) const
 	{
-		// the boundary: the middle of the columns right of the next panel, taken at the middle step of this phase
-		idx_t kend = 0;
-		while (kend + 1 < nsteps && m - J[(size_t) kend + 1] >= LU_PIPE_FROM - 3072)
-			++kend;
-		const idx_t jm = Jat(kend / 2 + 2);
-		jA = (jm + n) / 2 / LU_LA_NB * LU_LA_NB;
+		const idx_t j0 = plan.J[(size_t) k], j1 = plan.J[(size_t) k + 1], w = j1 - j0;
+		const idx_t j2 = plan.at(k + 2), w2 = j2 - j1, w3 = plan.at(k + 3) - j2;
+		const idx_t jA = plan.jA;
+		const bool bulk_bound = plan.bulk_bound(m - j1), staged = handed != LuPanelForm::Plain;
+		LuBulk bulk = LuBulk::Last;
+		// Pipelining pays while a product is much longer than a chain: down to 13312 rows below the panel (N = 16384: the first
+		// six steps; 89.7-90.1 -> 88.2-88.5 ms; down to 10240 rows 89.0 -- later the chains, which run 2-4 x slower among a
+		// product's workgroups, no longer fit beside half a product: profiles/r05_exp_lu_driver.txt).
+		if (w2 > 0 && bulk_bound && side && !staged && m > j1 && j2 + 2 * LU_LA_NB <= jA && jA < n && m - j1 >= plan.pipe_from)
+			bulk = LuBulk::Pipelined;
+		else if (w2 > 0 && staged)
+			bulk = handed == LuPanelForm::FlatStaged ? LuBulk::StagedLeaf : LuBulk::StagedHalf;
+		else if (w2 > 0 && bulk_bound && side && j2 < n && m > j1)
+			bulk = LuBulk::SideChain;
+		else if (w2 > 0 && bulk_bound)
+			bulk = LuBulk::OneChain;
+		else if (w2 > 0)
+			bulk = LuBulk::Plain;
+		// While the panel chain is the critical one, what sits between two panels is the bulk stream's chain "interchanges,
+		// solve against the 512 x 512 triangle, product" on the next panel's columns (~330 us, profiles/r04_lu_timeline.txt).
+		// Most of it can run early: as soon as a part of panel k + 1 is final, the bulk stream (idle in this phase) applies it
+		// to the columns of panel k + 2 (a stage: LuUpdate by that part's pivots) beside the rest of the panel; only the last
+		// part's stage (bulk_staged_tail) is left between the panels.  Row interchanges of later parts commute with a stage
+		// (they move whole rows of L and of the updated columns alike); the panel stream only has to wait for a stage before
+		// it interchanges rows of that part's columns (factor.rs:127-185), which the stage reads.
+		LuPanelForm panel = LuPanelForm::Plain;
+		if (w2 >= 256 && w2 % 256 == 0 && w3 > 0 && !plan.bulk_bound(m - j2) && m - j1 > w2) {
+			StreamScope sc(c.la_panel); // (flat_panel_ok asks for the leaf width on the stream the panel will run on)
+			panel = flat_panel_ok<T>(A.sub(j1, j1, m - j1, w2), wk) ? LuPanelForm::FlatStaged : LuPanelForm::RecStaged;
+		}
+		return Step{j0, j1, j2, w, w2, w3, bulk, panel};
 	}
-	hipEvent_t ev_GA_prev = nullptr, ev_GB_prev = nullptr; // the previous step's products on the two groups (bulk stream)
-	c.qr_side_streams();
-	hipStream_t side = c.qr_side[0];
-	// remaining rows from which the bulk stream is the critical one (mode 2 below); fewer: the panel chain is
-	auto bulk_bound = [&](idx_t rows_below) { return rows_below >= LU_LA_NB2_FROM; };
-	// one panel on the current stream: flat right-looking (getrf_panel_flat) where its shape allows, else the recursion
-	auto panel = [&](MatV<T> P, idx_t j) {
-		if (flat_panel_ok<T>(P, wk))
-			getrf_panel_flat<T>(P, (int) j, (int) j, wk, [](idx_t) { return (idx_t) 0; }, [](idx_t) {});
+
+	hipEvent_t record(hipStream_t s)
+	{
+		hipEvent_t e = c.next_event();
+		FH_HIP(hipEventRecord(e, s));
+		return e;
+	}
+	// the update by the pivots [r0, r0 + qw); `list`: &full once panel k's interchanges are composed there
+	LuUpdate<T> block(idx_t r0, idx_t qw, const LaswpList *list) const { return LuUpdate<T>{A, r0, qw, wk.piv + r0, (int) r0, list}; }
+	void compose(const Step &s) { laswp_compose_list(wk.piv + s.j0, (int) s.w, (int) s.j0, full); }
+
+	// ---- bulk side.  Each kind leaves ev_next behind the update of the next panel's columns.
+	// Between two trailing products the bulk stream used to run the chain "interchanges, solve, product" for the next panel's
+	// columns (~0.3 ms busy) and then wait for the side stream's chain on the far columns (~0.25 ms idle): ~0.55 ms per step in
+	// which most of the chip does nothing.  The columns right of the panel are cut at a fixed column jA into a near group A (with
+	// the next panel's columns) and a far group B, and ALL chains run on the side stream one product ahead: the chain of step
+	// k + 1 on A runs beside the product of step k on B, the chain on B beside the product of step k + 1 on A.  The bulk stream
+	// issues nothing but the two products per step.
+	void bulk_pipelined(const Step &s)
+	{
+		const idx_t jA = plan.jA;
+		hipEvent_t ev_cA = c.next_event(), ev_cB = c.next_event();
+		{
+			StreamScope ss(side);
+			stream_wait(side, ev_panel);
+			compose(s);
+			if (ev_GA_prev)
+				stream_wait(side, ev_GA_prev);
+			// near group + the next panel's columns: one chain, then the product on the next panel's columns
+			u.swaps(s.j1, jA - s.j1);
+			u.solve(s.j1, jA - s.j1);
+			FH_HIP(hipEventRecord(ev_cA, side)); // (the bulk stream's product on A waits for the solve only)
+			u.product(s.j1, s.w2);
+			ev_next = record(side);
+			if (ev_GB_prev)
+				stream_wait(side, ev_GB_prev);
+			u.swaps(jA, n - jA);
+			u.solve(jA, n - jA);
+			FH_HIP(hipEventRecord(ev_cB, side));
+		}
+		stream_wait(c.la_bulk, ev_cA);
+		u.product(s.j2, jA - s.j2); // (a pipelined step has jA >= j2 + 2 LU_LA_NB)
+		ev_GA_prev = record(c.la_bulk);
+		stream_wait(c.la_bulk, ev_cB);
+		u.product(jA, n - jA);
+		ev_GB_prev = record(c.la_bulk);
+	}
+	// last stage of the staged update of the next panel's columns (the earlier one ran beside the rest of panel k, panel_*_staged)
+	void bulk_staged_tail(const Step &s)
+	{
+		// the last LEAF of panel k is all that is left (the next panel's columns sit right behind the leaf's): two launches on the
+		// whole chip between two panels instead of "interchanges, substitution leaf, product" for 128 pivots; else its second half
+		if (s.bulk == LuBulk::StagedLeaf)
+			lu_node_update<T>(A, 0, 0, s.j1 - LUN_W, s.w2, wk, true);
 		else
-			getrf_rec<T>(P, (int) j, (int) j, wk);
-	};
-	bool staged = false; // the panel about to be applied has already been applied to the next panel's columns except for its last part
-	idx_t staged_last = 0; // ... whose width this is (half the panel, or one leaf: see the panel part below)
-	{
-		StreamScope sc(c.la_panel);
-		panel(A.sub(0, 0, m, J[1]), 0);
-		ev_panel = c.next_event();
-		FH_HIP(hipEventRecord(ev_panel, c.la_panel));
+			block(s.j0 + s.w / 2, s.w / 2, nullptr)(s.j1, s.w2);
+		ev_next = record(c.la_bulk);
+		compose(s); // (behind the release of the next panel)
+		if (s.j2 < n)
+			u(s.j2, n - s.j2);
 	}
-	// the interchanges of panel k (pivots [j0, j0 + w)) on the columns [c0, c0 + nc), rows j0 ..
-	auto swaps = [&](idx_t k, idx_t j0, idx_t w, idx_t c0, idx_t nc) {
-		(void) k;
-		(void) w;
-		laswp_list_dev<T>(A.sub(j0, c0, m - j0, nc), full);
-	};
-	// brings the columns [c0, c0 + nc) up to date with panel k = [j0, j0 + w): swaps, solve, update
-	auto update = [&](idx_t k, idx_t j0, idx_t w, idx_t c0, idx_t nc) {
-		const idx_t j1 = j0 + w;
-		swaps(k, j0, w, c0, nc);
-		MatV<T> U = A.sub(j0, c0, w, nc);
-		trsm_lower_dev<T>(A.sub(j0, j0, w, w).c(), true, U);
-		if (m > j1)
-			gemm_dev<T>(A.sub(j1, c0, m - j1, nc), DST_FULL, true, A.sub(j1, j0, m - j1, w).c(), U.c(), (T) -1);
-	};
-	// ---- staged update of the NEXT panel's columns (while the panel chain is the critical one, see the panel part below).
-	// Stage q of panel [jp, jp + 512) on the columns [cx, cx + wx): the interchanges of its pivots [q QW, (q + 1) QW), the solve
-	// against that diagonal block, the product with the QW columns below it -- on the bulk stream.
-	// QW = 256 (two stages): with four stages of 128 the part left between two panels is shorter, but the factorization is 2 - 3 ms
-	// SLOWER at N = 8192 .. 16384 (profiles/r04_exp_lu_stages.txt): twice the small launches beside the latency-bound panel kernel
-	idx_t QW = 256; // (half of the panel being staged; set per step)
-	hipEvent_t ev_stage[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-	// (general form: the pivots / columns [r0, r0 + qw) of the panel)
-	auto stage_update_at = [&](idx_t r0, idx_t qw, idx_t cx, idx_t wx) {
-		const idx_t r1 = r0 + qw;
-		laswp_dev<T>(A.sub(r0, cx, m - r0, wx), wk.piv + r0, (int) qw, (int) r0);
-		MatV<T> U = A.sub(r0, cx, qw, wx);
-		trsm_lower_dev<T>(A.sub(r0, r0, qw, qw).c(), true, U);
-		if (m > r1)
-			gemm_dev<T>(A.sub(r1, cx, m - r1, wx), DST_FULL, true, A.sub(r1, r0, m - r1, qw).c(), U.c(), (T) -1);
-	};
-	auto stage_update = [&](idx_t jp, idx_t q, idx_t cx, idx_t wx) { stage_update_at(jp + q * QW, QW, cx, wx); };
-	// The panel [jp, jp + 512) on the panel stream with the top levels of getrf_rec's recursion written out (factor.rs:84-117,
-	// :127-185), columns [lo, hi) of it: as soon as a QW-column part is final, its stage starts on the bulk stream; the
-	// interchanges a later part makes on that part's columns wait for the stage, which reads them.
-	std::function<void(idx_t, idx_t, idx_t, idx_t, idx_t)> staged_panel = [&](idx_t jp, idx_t cx, idx_t wx, idx_t lo, idx_t hi) {
-		if (hi - lo == QW) {
-			getrf_rec<T>(A.sub(jp + lo, jp + lo, m - jp - lo, QW), (int) (jp + lo), (int) (jp + lo), wk);
-			const idx_t q = lo / QW;
-			if (hi < 2 * QW) { // (the last part's stage opens the next step on the bulk stream)
-				hipEvent_t ev_part = c.next_event();
-				FH_HIP(hipEventRecord(ev_part, c.la_panel));
-				StreamScope sb(c.la_bulk);
-				stream_wait(c.la_bulk, ev_part);
-				stage_update(jp, q, cx, wx);
-				ev_stage[q] = c.next_event();
-				FH_HIP(hipEventRecord(ev_stage[q], c.la_bulk));
-			}
+	// the chain of the columns behind the next panel -- interchanges, solve -- on the side stream, BESIDE the bulk stream's chain
+	// and product for the next panel's columns: both chains are latency bound (a dozen small launches each), together they keep
+	// the chip no busier than one, and the big product starts a chain earlier
+	void bulk_side_chain(const Step &s)
+	{
+		hipEvent_t ev_list = c.next_event(), ev_side = c.next_event();
+		FH_HIP(hipEventRecord(ev_list, c.la_bulk)); // (the list is composed, everything earlier on these columns is done)
+		{
+			StreamScope ss(side);
+			stream_wait(side, ev_list);
+			u.swaps(s.j2, n - s.j2);
+			u.solve(s.j2, n - s.j2);
+			FH_HIP(hipEventRecord(ev_side, side));
+		}
+		u(s.j1, s.w2);
+		ev_next = record(c.la_bulk);
+		stream_wait(c.la_bulk, ev_side);
+		u.product(s.j2, n - s.j2);
+	}
+	// ONE chain of interchanges + solve for all columns right of the panel, then the product on the next panel's columns
+	// (-> released), then on the rest
+	void bulk_one_chain(const Step &s)
+	{
+		u.swaps(s.j1, n - s.j1);
+		u.solve(s.j1, n - s.j1);
+		u.product(s.j1, s.w2);
+		ev_next = record(c.la_bulk);
+		if (s.j2 < n)
+			u.product(s.j2, n - s.j2);
+	}
+	// (all 512 columns of the next panel at once: with the wave-panel leaf the split "first 64, then 448" of rounds 1-3 made the
+	// panel wait for the second chain)
+	void bulk_plain(const Step &s)
+	{
+		u(s.j1, s.w2);
+		ev_next = record(c.la_bulk);
+		if (s.j2 < n)
+			u(s.j2, n - s.j2);
+	}
+
+	// ---- panel side: the next panel, [j1, j2)
+	// Stage q: as soon as the part [r0, r0 + qw) of the panel is final on the panel stream, the bulk stream applies it to the
+	// columns [cx, cx + wx) of the panel after it.  Two stages per panel: with four stages of 128 the part left between two
+	// panels is shorter, but the factorization is 2 - 3 ms SLOWER at N = 8192 .. 16384 (profiles/r04_exp_lu_stages.txt): twice the
+	// small launches beside the latency-bound panel kernel.
+	void start_stage(idx_t q, idx_t r0, idx_t qw, idx_t cx, idx_t wx)
+	{
+		stream_wait(c.la_bulk, record(c.la_panel));
+		StreamScope sb(c.la_bulk);
+		block(r0, qw, nullptr)(cx, wx);
+		ev_stage[q] = record(c.la_bulk);
+	}
+	// the flat panel in two parts: the first is everything but the LAST LEAF -- its stage runs beside that leaf, and what is left
+	// between two panels is one leaf's worth of interchanges + one fused node launch (flat_panel_ok: the node kernel can address
+	// the panel); the second part's interchanges on the first part's columns wait for the stage
+	void panel_flat_staged(const Step &s)
+	{
+		const idx_t j1 = s.j1, w2 = s.w2;
+		const idx_t s0 = w2 - LUN_W; // width of the first part
+		getrf_panel_flat<T>(A.sub(j1, j1, m - j1, w2), (int) j1, (int) j1, wk, s0, [&] { start_stage(0, j1, s0, s.j2, s.w3); });
+		stream_wait(c.la_panel, ev_stage[0]);
+		laswp_dev<T>(A.sub(j1 + s0, j1, m - j1 - s0, s0), wk.piv + j1 + s0, (int) LUN_W, (int) (j1 + s0));
+	}
+	// The panel [jp, jp + 2 qw) with the top levels of getrf_rec's recursion written out (factor.rs:84-117, :127-185), columns
+	// [lo, hi) of it: as soon as a qw-column part is final, its stage on the columns [cx, cx + wx) starts; the interchanges a
+	// later part makes on that part's columns wait for the stage, which reads them.
+	void staged_panel(idx_t jp, idx_t qw, idx_t cx, idx_t wx, idx_t lo, idx_t hi)
+	{
+		if (hi - lo == qw) {
+			getrf_rec<T>(A.sub(jp + lo, jp + lo, m - jp - lo, qw), (int) (jp + lo), (int) (jp + lo), wk);
+			if (hi < 2 * qw) // (the last part's stage opens the next step on the bulk stream)
+				start_stage(lo / qw, jp + lo, qw, cx, wx);
 			return;
 		}
 		const idx_t mid = (lo + hi) / 2;
-		staged_panel(jp, cx, wx, lo, mid);
-		const idx_t a = jp + lo, b = jp + mid;
-		laswp_dev<T>(A.sub(a, b, m - a, hi - mid), wk.piv + a, (int) (mid - lo), (int) a);
-		MatV<T> U = A.sub(a, b, mid - lo, hi - mid);
-		trsm_lower_dev<T>(A.sub(a, a, mid - lo, mid - lo).c(), true, U);
-		gemm_dev<T>(A.sub(b, b, m - b, hi - mid), DST_FULL, true, A.sub(b, a, m - b, mid - lo).c(), U.c(), (T) -1);
-		staged_panel(jp, cx, wx, mid, hi);
-		stream_wait(c.la_panel, ev_stage[mid / QW - 1]); // (bulk stream order: the earlier stages are done as well)
-		laswp_dev<T>(A.sub(b, a, m - b, mid - lo), wk.piv + b, (int) (hi - mid), (int) b);
-	};
-	for (idx_t k = 0; k < nsteps; ++k) {
-		const idx_t j0 = J[(size_t) k], j1 = J[(size_t) k + 1], w = j1 - j0;
-		const idx_t j2 = Jat(k + 2), w2 = j2 - j1;
-		hipEvent_t ev_next = nullptr;
-		use_list(k);
+		staged_panel(jp, qw, cx, wx, lo, mid);
+		block(jp + lo, mid - lo, nullptr)(jp + mid, hi - mid);
+		staged_panel(jp, qw, cx, wx, mid, hi);
+		stream_wait(c.la_panel, ev_stage[mid / qw - 1]); // (bulk stream order: the earlier stages are done as well)
+		laswp_dev<T>(A.sub(jp + mid, jp + lo, m - jp - mid, mid - lo), wk.piv + jp + mid, (int) (hi - mid), (int) (jp + mid));
+	}
+
+	void run()
+	{
+		c.reset_events();
+		hipEvent_t e0 = record(caller);
+		stream_wait(c.la_bulk, e0);
+		stream_wait(c.la_panel, e0);
+		c.qr_side_streams();
+		side = c.qr_side[0];
 		{
-			StreamScope sc(c.la_bulk);
-			stream_wait(c.la_bulk, ev_panel);
-			// Every solve U = L_kk^-1 A is a dependent chain of ~8 launches whose length does not depend on the number of columns
-			// (profiles/r04_lu_v4_timeline.txt: ~240 us per chain, three chains per step -- the first 64 columns of the next panel,
-			// its other 448, the rest -- were 20 of the bulk stream's 87 ms).  How the columns right of the panel are grouped:
-			//   mode 2 (while the bulk stream is the critical one: its trailing product takes longer than a panel): ONE chain of
-			//          interchanges + solve for all of them, then the product on the next panel's columns (-> released), then on
-			//          the rest;
-			//   mode 1 (afterwards, the panel chain is critical): the next panel's columns first (all 512: with the round-4 leaf
-			//          the split "first 64, then 448" of rounds 1-3 made the panel wait for the second chain), then the rest.
-			// Measured in one visit (profiles/r04_exp_lu_chain_grouping.txt, N = 16384): three chains 107.9 ms, mode 1 everywhere
-			// 102.4, mode 2 everywhere 101.6, mode 2 down to 10240 remaining rows 100.7.
-			const int mode = bulk_bound(m - j1) ? 2 : 1;
-			auto compose = [&]() { laswp_compose_list(wk.piv + j0, (int) w, (int) j0, full); };
-			const bool pipe = w2 > 0 && mode == 2 && side && !staged && m > j1 && j2 + 2 * LU_LA_NB <= jA && jA < n && m - j1 >= LU_PIPE_FROM;
-			if (!pipe && !(w2 > 0 && staged)) // (the staged path composes it behind the release of the next panel)
-				compose();
-			if (pipe) {
-				hipEvent_t ev_cA = c.next_event(), ev_cB = c.next_event();
-				{
-					StreamScope ss(side);
-					stream_wait(side, ev_panel);
-					compose();
-					if (ev_GA_prev)
-						stream_wait(side, ev_GA_prev);
-					// near group + the next panel's columns: one chain, then the product on the next panel's columns
-					swaps(k, j0, w, j1, jA - j1);
-					MatV<T> U = A.sub(j0, j1, w, jA - j1);
-					trsm_lower_dev<T>(A.sub(j0, j0, w, w).c(), true, U);
-					FH_HIP(hipEventRecord(ev_cA, side)); // (the bulk stream's product on A waits for the solve only)
-					gemm_dev<T>(A.sub(j1, j1, m - j1, w2), DST_FULL, true, A.sub(j1, j0, m - j1, w).c(), U.sub(0, 0, w, w2).c(), (T) -1);
-					ev_next = c.next_event();
-					FH_HIP(hipEventRecord(ev_next, side));
-					if (ev_GB_prev)
-						stream_wait(side, ev_GB_prev);
-					swaps(k, j0, w, jA, n - jA);
-					trsm_lower_dev<T>(A.sub(j0, j0, w, w).c(), true, A.sub(j0, jA, w, n - jA));
-					FH_HIP(hipEventRecord(ev_cB, side));
-				}
-				stream_wait(c.la_bulk, ev_cA);
-				if (jA > j2)
-					gemm_dev<T>(A.sub(j1, j2, m - j1, jA - j2), DST_FULL, true, A.sub(j1, j0, m - j1, w).c(), A.sub(j0, j2, w, jA - j2).c(), (T) -1);
-				ev_GA_prev = c.next_event();
-				FH_HIP(hipEventRecord(ev_GA_prev, c.la_bulk));
-				stream_wait(c.la_bulk, ev_cB);
-				gemm_dev<T>(A.sub(j1, jA, m - j1, n - jA), DST_FULL, true, A.sub(j1, j0, m - j1, w).c(), A.sub(j0, jA, w, n - jA).c(), (T) -1);
-				ev_GB_prev = c.next_event();
-				FH_HIP(hipEventRecord(ev_GB_prev, c.la_bulk));
-			} else
-			if (w2 > 0 && staged) {
-				// last stage of the staged update of the next panel's columns (the earlier ones ran beside the rest of panel k,
-				// see the panel part below): interchanges of the last QW pivots, U = L_qq^-1 (.), product with K = QW
-				if (staged_last == LUN_W) {
-					// the last LEAF of panel k is all that is left: its interchanges (which also gather the top block) and ONE
-					// launch of the fused node kernel on the next panel's columns, which sit right behind the leaf's -- two launches
-					// on the whole chip between two panels instead of "interchanges, substitution leaf, product" for 128 pivots
-					const idx_t r0 = j1 - LUN_W;
-					FH_CHECK(w2 <= LU_FLAT_MAXW, "lu: more column groups than LuWork::ttop holds");
-					laswp_dev<T>(A.sub(r0, j1, m - r0, w2), wk.piv + r0, (int) LUN_W, (int) r0, wk.ttop, (const T *) (A.p + r0 * A.rs + r0 * A.cs), A.cs);
-					const idx_t below = m - r0 - LUN_W;
-					unsigned nwg = below > 0 ? (unsigned) ((below + LUN_ROWS - 1) / LUN_ROWS) : 1u;
-					const unsigned ncg = (unsigned) ((w2 + LUN_W - 1) / LUN_W);
-					const unsigned cap = (unsigned) (2 * ctx().stream_cus()) / ncg;
-					if (nwg > cap)
-						nwg = cap < 1u ? 1u : cap;
-					hipLaunchKernelGGL(lu_node64_kernel<T>, dim3(nwg, ncg), dim3(256), 0, ctx().stream, A.p + r0 * A.rs + r0 * A.cs, A.cs, (int) (m - r0), (int) w2,
-							   (const T *) wk.ttop, 1);
-					FH_HIP(hipGetLastError());
-				} else {
-					QW = w / 2;
-					stage_update(j0, 1, j1, w2);
-				}
-				ev_next = c.next_event();
-				FH_HIP(hipEventRecord(ev_next, c.la_bulk));
-				compose();
-				if (j2 < n)
-					update(k, j0, w, j2, n - j2);
-			} else if (w2 > 0 && mode == 2 && side && j2 < n && m > j1) {
-				// the chain of the columns behind the next panel -- interchanges, solve -- on the side stream, BESIDE the bulk
-				// stream's chain and product for the next panel's columns: both chains are latency bound (a dozen small launches
-				// each), together they keep the chip no busier than one, and the big product starts a chain earlier
-				hipEvent_t ev_list = c.next_event(), ev_side = c.next_event();
-				FH_HIP(hipEventRecord(ev_list, c.la_bulk)); // (the list is composed, everything earlier on these columns is done)
-				{
-					StreamScope ss(side);
-					stream_wait(side, ev_list);
-					swaps(k, j0, w, j2, n - j2);
-					trsm_lower_dev<T>(A.sub(j0, j0, w, w).c(), true, A.sub(j0, j2, w, n - j2));
-					FH_HIP(hipEventRecord(ev_side, side));
-				}
-				update(k, j0, w, j1, w2);
-				ev_next = c.next_event();
-				FH_HIP(hipEventRecord(ev_next, c.la_bulk));
-				stream_wait(c.la_bulk, ev_side);
-				gemm_dev<T>(A.sub(j1, j2, m - j1, n - j2), DST_FULL, true, A.sub(j1, j0, m - j1, w).c(), A.sub(j0, j2, w, n - j2).c(), (T) -1);
-			} else if (w2 > 0 && mode == 2) {
-				swaps(k, j0, w, j1, n - j1);
-				MatV<T> U = A.sub(j0, j1, w, n - j1);
-				trsm_lower_dev<T>(A.sub(j0, j0, w, w).c(), true, U);
-				if (m > j1)
-					gemm_dev<T>(A.sub(j1, j1, m - j1, w2), DST_FULL, true, A.sub(j1, j0, m - j1, w).c(), U.sub(0, 0, w, w2).c(), (T) -1);
-				ev_next = c.next_event();
-				FH_HIP(hipEventRecord(ev_next, c.la_bulk));
-				if (j2 < n && m > j1)
-					gemm_dev<T>(A.sub(j1, j2, m - j1, n - j2), DST_FULL, true, A.sub(j1, j0, m - j1, w).c(), U.sub(0, w2, w, n - j2).c(), (T) -1);
-			} else if (w2 > 0) {
-				update(k, j0, w, j1, w2);
-				ev_next = c.next_event();
-				FH_HIP(hipEventRecord(ev_next, c.la_bulk));
-				if (j2 < n)
-					update(k, j0, w, j2, n - j2);
-			}
-			if (!pipe) { // (a pipelined step that followed would order its chains behind this step's bulk work)
-				ev_GA_prev = ev_GB_prev = c.next_event();
-				FH_HIP(hipEventRecord(ev_GA_prev, c.la_bulk));
-			}
-			// factor.rs:127-185: the panel's transpositions act on the columns to its left as well (nothing reads those columns
-			// again during the factorization; on the plain side stream instead these passes made the factorization 1.2 ms slower,
-			// composed over 8 panels they cost a serial tail: profiles/r05_exp_lu_driver.txt, r02_exp_lu_panel.txt)
-			if (j0 > 0)
-				swaps(k, j0, w, 0, j0);
+			StreamScope sc(c.la_panel);
+			getrf_panel<T>(A.sub(0, 0, m, plan.J[1]), 0, 0, wk);
+			ev_panel = record(c.la_panel);
 		}
-		if (w2 > 0) {
+		for (idx_t k = 0; k < plan.nsteps(); ++k) {
+			const Step s = decide(k);
+			full.dst = listb.as<int>() + (size_t) (k % NLIST) * 4 * LU_LA_NB;
+			full.src = full.dst + 2 * LU_LA_NB;
+			u = block(s.j0, s.w, &full);
+			{
+				StreamScope sc(c.la_bulk);
+				stream_wait(c.la_bulk, ev_panel);
+				const bool tail = s.bulk == LuBulk::StagedLeaf || s.bulk == LuBulk::StagedHalf;
+				if (s.bulk != LuBulk::Pipelined && !tail) // (those two compose the list later, on their own terms)
+					compose(s);
+				if (s.bulk == LuBulk::Pipelined)
+					bulk_pipelined(s);
+				else if (tail)
+					bulk_staged_tail(s);
+				else if (s.bulk == LuBulk::SideChain)
+					bulk_side_chain(s);
+				else if (s.bulk == LuBulk::OneChain)
+					bulk_one_chain(s);
+				else if (s.bulk == LuBulk::Plain)
+					bulk_plain(s);
+				if (s.bulk != LuBulk::Pipelined) // (a pipelined step that followed would order its chains behind this step's bulk work)
+					ev_GA_prev = ev_GB_prev = record(c.la_bulk);
+				// factor.rs:127-185: the panel's transpositions act on the columns to its left as well (nothing reads those columns
+				// again during the factorization; on the plain side stream instead these passes made the factorization 1.2 ms slower,
+				// composed over 8 panels they cost a serial tail: profiles/r05_exp_lu_driver.txt, r02_exp_lu_panel.txt)
+				if (s.j0 > 0)
+					u.swaps(0, s.j0);
+			}
+			handed = s.panel;
+			if (s.w2 == 0) // (there is no next panel)
+				continue;
 			StreamScope sc(c.la_panel);
 			stream_wait(c.la_panel, ev_next);
-			// While the panel chain is the critical one, what sits between two panels is the bulk stream's chain "interchanges,
-			// solve against the 512 x 512 triangle, product" on the next panel's columns (~330 us, profiles/r04_lu_timeline.txt).
-			// Most of it can run early: as soon as a QW-column part of panel k + 1 is final, the bulk stream (idle in this
-			// phase) applies it to the columns of panel k + 2 -- interchanges of its QW pivots, U = L_qq^-1 (.), product with
-			// K = QW on all rows below -- beside the rest of the panel; only the last part's stage (above) is left between the
-			// panels.  Row interchanges of later parts commute with a stage (they move whole rows of L and of the updated columns
-			// alike); the panel stream only has to wait for a stage before it interchanges rows of that part's columns
-			// (factor.rs:127-185), which the stage reads.
-			const idx_t w3 = Jat(k + 3) - j2;
-			const bool stage = w2 >= 256 && w2 % 256 == 0 && w3 > 0 && !bulk_bound(m - j2) && m - j1 > w2;
-			MatV<T> Pn = A.sub(j1, j1, m - j1, w2);
-			if (!stage) {
-				panel(Pn, j1);
-			} else if (flat_panel_ok<T>(Pn, wk)) {
-				// the flat panel in two parts: as soon as the left half is final -- its leaves' interchanges applied inside the
-				// half -- the bulk stream starts stage 0; the right half's interchanges on the left half's columns wait for it
-				// (round 5, second half: the first part is everything but the LAST LEAF -- its stage runs beside that leaf, and what is
-				// left between two panels is one leaf's worth of interchanges + one fused node launch; halves before)
-				const idx_t nl = w2 / LUN_W;
-				const idx_t s0 = lu_node_offsets_ok<T>(m - j1, A.cs) ? w2 - LUN_W : w2 / 2; // width of the first part
-				const idx_t lp0 = s0 / LUN_W;						    // its leaves
-				(void) nl;
-				getrf_panel_flat<T>(
-					Pn, (int) j1, (int) j1, wk, [&](idx_t jl) { return jl < lp0 ? (idx_t) 0 : s0; },
-					[&](idx_t jl) {
-						if (jl + 1 == lp0) {
-							hipEvent_t ev_part = c.next_event();
-							FH_HIP(hipEventRecord(ev_part, c.la_panel));
-							StreamScope sb(c.la_bulk);
-							stream_wait(c.la_bulk, ev_part);
-							stage_update_at(j1, s0, j2, w3);
-							ev_stage[0] = c.next_event();
-							FH_HIP(hipEventRecord(ev_stage[0], c.la_bulk));
-						}
-					});
-				stream_wait(c.la_panel, ev_stage[0]);
-				laswp_dev<T>(A.sub(j1 + s0, j1, m - j1 - s0, s0), wk.piv + j1 + s0, (int) (w2 - s0), (int) (j1 + s0));
-				staged_last = w2 - s0;
-			} else {
-				QW = w2 / 2;
-				staged_panel(j1, j2, w3, 0, w2);
-				staged_last = QW;
-			}
-			staged = stage;
-			ev_panel = c.next_event();
-			FH_HIP(hipEventRecord(ev_panel, c.la_panel));
-		} else {
-			staged = false;
+			if (s.panel == LuPanelForm::Plain)
+				getrf_panel<T>(A.sub(s.j1, s.j1, m - s.j1, s.w2), (int) s.j1, (int) s.j1, wk);
+			else if (s.panel == LuPanelForm::FlatStaged)
+				panel_flat_staged(s);
+			else
+				staged_panel(s.j1, s.w2 / 2, s.j2, s.w3, 0, s.w2);
+			ev_panel = record(c.la_panel);
 		}
+		stream_wait(caller, record(c.la_bulk));
+		stream_wait(caller, record(c.la_panel)); // (everything on the panel stream)
 	}
-	hipEvent_t eb = c.next_event();
-	FH_HIP(hipEventRecord(eb, c.la_bulk));
-	stream_wait(caller, eb);
-	hipEvent_t ep = c.next_event(); // (everything on the panel stream)
-	FH_HIP(hipEventRecord(ep, c.la_panel));
-	stream_wait(caller, ep);
-}
+};
 
 template <typename T> long getrf_dev(MatV<T> A, idx_t *perm, idx_t *perm_inv)
 {
@@ -1757,23 +1822,7 @@ template <typename T> long getrf_dev(MatV<T> A, idx_t *perm, idx_t *perm_inv)
 	const idx_t size = m < n ? m : n;
 	long n_trans = 0;
 	if (size > 0) {
-		Scratch pivb((size_t) size * sizeof(int));
-		const size_t gran_bytes = (size_t) LU2_NSLOT * LU2_GMAX * LU2_GSLOT * sizeof(xwg_u64), diag_bytes = (size_t) LU2_NSLOT * 2 * LU_WMAX * sizeof(xwg_u64);
-		Scratch granb(gran_bytes + diag_bytes);
-		Scratch misc(256);
-		Scratch wwsb(LW_WS_BYTES);
-		Scratch ttopb((size_t) LUN_W * LU_FLAT_MAXW * sizeof(T));
-		LuWork<T> wk;
-		wk.wws = wwsb.as<unsigned char>();
-		wk.ttop = ttopb.as<T>();
-		FH_HIP(hipMemsetAsync(wwsb.p, 0, LW_WS_BYTES, ctx().stream));
-		wk.piv = pivb.as<int>();
-		wk.gran = granb.as<xwg_u64>();
-		wk.gran_diag = wk.gran + (size_t) LU2_NSLOT * LU2_GMAX * LU2_GSLOT;
-		wk.epoch_base = 0;
-		wk.status = misc.as<int>() + 8;
-		FH_HIP(hipMemsetAsync(misc.p, 0, 256, ctx().stream));
-		FH_HIP(hipMemsetAsync(granb.p, 0, gran_bytes + diag_bytes, ctx().stream));
+		LuWork<T> wk(size, nullptr, nullptr);
 
 		// The cooperative leaves exchange pivots between RESIDENT workgroups.  Residency is arranged, not hoped for: a leaf is
 		// only launched with at most one workgroup per compute unit its stream can use (leaf_width_for / resident_workgroups,
@@ -1804,11 +1853,9 @@ template <typename T> long getrf_dev(MatV<T> A, idx_t *perm, idx_t *perm_inv)
 		const idx_t la_min = g_lu_plan_la_min.load() > 0 ? (idx_t) g_lu_plan_la_min.load() : 8 * LU_LA_NB;
 		const bool la = !force_general && size >= la_min && ctx().lookahead_streams() && (m + leaf_r - 1) / leaf_r <= (idx_t) ctx().la_panel_cus;
 		if (la)
-			getrf_lookahead<T>(A.sub(0, 0, m, size), wk, ctx().stream);
-		else if (flat_panel_ok<T>(A.sub(0, 0, m, size), wk)) // (one panel of the look-ahead driver: same launches, same pivots)
-			getrf_panel_flat<T>(A.sub(0, 0, m, size), 0, 0, wk, [](idx_t) { return (idx_t) 0; }, [](idx_t) {});
+			LuLookahead<T>{A.sub(0, 0, m, size), wk, ctx().stream}.run();
 		else
-			getrf_rec<T>(A.sub(0, 0, m, size), 0, 0, wk);
+			getrf_panel<T>(A.sub(0, 0, m, size), 0, 0, wk);
 		if (lent && !force_general) {
 			int st2[4] = {0, 0, 0, 0};
 			FH_HIP(hipMemcpyAsync(st2, wk.status, sizeof(st2), hipMemcpyDeviceToHost, ctx().stream));
@@ -1818,16 +1865,13 @@ template <typename T> long getrf_dev(MatV<T> A, idx_t *perm, idx_t *perm_inv)
 				fprintf(stderr, "faer_hip: partial_piv_lu: the cross-workgroup exchange of the panel kernel timed out (GPU shared with other "
 						"work?); redoing the factorization from the lent copy on the non-cooperative path\n");
 				copy_dev<T>(A, MatV<const T>{lent, m, n, 1, m});
-				FH_HIP(hipMemsetAsync(misc.p, 0, 256, ctx().stream));
+				wk.clear_status();
 				wk.general = true;
 				getrf_rec<T>(A.sub(0, 0, m, size), 0, 0, wk);
 			}
 		}
-		if (m < n) { // factor.rs:278-285 (+ the swaps of the columns right of the square part)
-			MatV<T> right = A.sub(0, size, m, n - size);
-			laswp_dev<T>(right, wk.piv, (int) size, 0);
-			trsm_lower_dev<T>(A.sub(0, 0, size, size).c(), true, right);
-		}
+		if (m < n) // factor.rs:278-285 (+ the swaps of the columns right of the square part)
+			LuUpdate<T>{A, 0, size, wk.piv, 0, nullptr}(size, n - size);
 		std::vector<int> piv((size_t) size);
 		int st[4] = {0, 0, 0, 0};
 		FH_HIP(hipMemcpyAsync(piv.data(), wk.piv, (size_t) size * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
@@ -1868,27 +1912,8 @@ template <typename T> void getrf_panel_dev(MatV<T> P, int *piv_dev, int *status_
 	FH_CHECK(w <= m, "getrf_panel: the panel must be tall");
 	if (w == 0)
 		return;
-	const size_t gran_bytes = (size_t) LU2_NSLOT * LU2_GMAX * LU2_GSLOT * sizeof(xwg_u64), diag_bytes = (size_t) LU2_NSLOT * 2 * LU_WMAX * sizeof(xwg_u64);
-	// released on return while the kernels may still be queued: the pool hands a buffer back to the SAME stream only
-	Scratch granb(gran_bytes + diag_bytes);
-	Scratch misc(256);
-	Scratch wwsb(LW_WS_BYTES);
-	Scratch ttopb((size_t) LUN_W * LU_FLAT_MAXW * sizeof(T));
-	LuWork<T> wk;
-	wk.wws = wwsb.as<unsigned char>();
-	wk.ttop = ttopb.as<T>();
-	FH_HIP(hipMemsetAsync(wwsb.p, 0, LW_WS_BYTES, ctx().stream));
-	wk.piv = piv_dev;
-	wk.gran = granb.as<xwg_u64>();
-	wk.gran_diag = wk.gran + (size_t) LU2_NSLOT * LU2_GMAX * LU2_GSLOT;
-	wk.epoch_base = 0;
-	wk.status = status_dev ? status_dev : misc.as<int>() + 8;
-	FH_HIP(hipMemsetAsync(misc.p, 0, 256, ctx().stream));
-	FH_HIP(hipMemsetAsync(granb.p, 0, gran_bytes + diag_bytes, ctx().stream));
-	if (flat_panel_ok<T>(P, wk)) // (the distributed driver's block columns: the flat right-looking panel of the look-ahead driver)
-		getrf_panel_flat<T>(P, 0, 0, wk, [](idx_t) { return (idx_t) 0; }, [](idx_t) {});
-	else
-		getrf_rec<T>(P, 0, 0, wk);
+	LuWork<T> wk(w, piv_dev, status_dev);
+	getrf_panel<T>(P, 0, 0, wk);
 	if (status_dev)
 		return;
 	int st[4] = {0, 0, 0, 0};

@@ -330,35 +330,44 @@ def test_plu_full_size_property(oracle):
 @pytest.mark.parametrize("m,n", [(4096, 4096), (4500, 4321), (6000, 5000)])
 def test_plu_lookahead_path(m, n):
     """min(m, n) >= 4096 runs the look-ahead LU driver (panel stream + bulk stream, 512-column steps, getrf.hip):
-    P A == L U entrywise, |L| <= 1, a valid permutation, and the bitwise same answer twice"""
+    P A == L U entrywise, |L| <= 1, a valid permutation, and the bitwise same answer twice -- for a column-major operand (flat
+    panels, handed over leaf-wise) and for the same values row major (row stride != 1: the recursion inside every panel, staged
+    panels handed over in halves), which must choose the identical permutation"""
     import torch
 
     F = init_gpu()
     g = torch.Generator(device="cuda").manual_seed(m + n)
-    a = torch.randn((n, m), dtype=torch.float64, device="cuda", generator=g).t()
-    lu = a.clone()
-    perm, perm_inv, _ = F.partial_piv_lu_factor_in_place(lu)
-    F.synchronize()
-    assert sorted(perm.tolist()) == list(range(m)) and all(perm[perm_inv[i]] == i for i in range(0, m, 97))
-    p = torch.as_tensor(perm.astype(np.int64), device="cuda")
-    size = min(m, n)
-    L = torch.tril(lu, -1)[:, :size]
-    L[:size, :size] += torch.eye(size, dtype=torch.float64, device="cuda")
-    U = torch.triu(lu)[:size, :]
-    assert torch.tril(lu, -1).abs().max().item() <= 1.0 + 1e-14
-    err = (L @ U - a[p]).abs().max().item()
-    assert err <= 16 * size * 2.3e-16 * (L.abs() @ U.abs()).max().item()
-    lu2 = a.clone()
-    perm2, _, _ = F.partial_piv_lu_factor_in_place(lu2)
-    F.synchronize()
-    assert np.array_equal(perm, perm2) and torch.equal(lu, lu2)
+    a_col = torch.randn((n, m), dtype=torch.float64, device="cuda", generator=g).t()
+    a_row = a_col.contiguous()
+    assert a_col.stride() == (1, m) and a_row.stride() == (n, 1)
+    perms = []
+    for a in (a_col, a_row):
+        lu = a.clone()
+        assert lu.stride() == a.stride()
+        perm, perm_inv, _ = F.partial_piv_lu_factor_in_place(lu)
+        F.synchronize()
+        assert sorted(perm.tolist()) == list(range(m)) and all(perm[perm_inv[i]] == i for i in range(0, m, 97))
+        p = torch.as_tensor(perm.astype(np.int64), device="cuda")
+        size = min(m, n)
+        L = torch.tril(lu, -1)[:, :size]
+        L[:size, :size] += torch.eye(size, dtype=torch.float64, device="cuda")
+        U = torch.triu(lu)[:size, :]
+        assert torch.tril(lu, -1).abs().max().item() <= 1.0 + 1e-14
+        err = (L @ U - a[p]).abs().max().item()
+        assert err <= 16 * size * 2.3e-16 * (L.abs() @ U.abs()).max().item()
+        lu2 = a.clone()
+        perm2, _, _ = F.partial_piv_lu_factor_in_place(lu2)
+        F.synchronize()
+        assert np.array_equal(perm, perm2) and torch.equal(lu, lu2)
+        perms.append(perm)
+    assert np.array_equal(perms[0], perms[1])
 
 
-@pytest.mark.parametrize("plan", [(2048, 3584, 2048), (1024, 100000, 2048), (100000, 100000, 2048), (512, 1536, 2048)])
+@pytest.mark.parametrize("plan", [(2048, 3584, 2048), (1024, 100000, 2048), (100000, 100000, 2048), (512, 1536, 2048), (256, 100000, 2048)])
 def test_plu_lookahead_phases_and_transitions_at_small_n(oracle, plan):
     """the look-ahead LU driver has three phases -- pipelined bulk-bound steps, plain bulk-bound steps, staged 256-column steps -- whose
     switch-over points sit at 9-13 k rows; `faer_hip_debug_lu_plan` moves them so that N = 5120 / 3072 runs every phase and every
-    transition.  Pivots and factors must not depend on the plan: identical permutation to the default plan's and to the
+    transition; the last plan keeps the step in front of the last panel bulk bound (one chain for all columns).  Pivots and factors must not depend on the plan: identical permutation to the default plan's and to the
     oracle's on the first panel, P A == L U, the bitwise same answer twice."""
     import torch
 
@@ -390,6 +399,24 @@ def test_plu_lookahead_phases_and_transitions_at_small_n(oracle, plan):
         ref = np.asfortranarray(a[:, :k].cpu().numpy())
         rperm, _, _ = oracle.lu_in_place(ref)
         assert (perm.astype(np.int64)[:k] == rperm[:k]).all()
+        # the same values row major (row stride != 1): the panels take the recursion, the staged steps the recursive staged panel
+        # and the half-panel tail.  Same assertions: the column-major run's permutation, P A == L U, the bitwise same answer twice
+        ar = a.contiguous()
+        assert ar.stride() == (n, 1)
+        F.lib().faer_hip_debug_lu_plan(C.c_size_t(nb2_from), C.c_size_t(pipe_from), C.c_size_t(la_min))
+        try:
+            lur = ar.clone()
+            permr, _, _ = F.partial_piv_lu_factor_in_place(lur)
+            lur2 = ar.clone()
+            permr2, _, _ = F.partial_piv_lu_factor_in_place(lur2)
+            F.synchronize()
+        finally:
+            F.lib().faer_hip_debug_lu_plan(C.c_size_t(0), C.c_size_t(0), C.c_size_t(0))
+        assert lur.stride() == (n, 1)
+        assert np.array_equal(permr, perm) and np.array_equal(permr, permr2) and torch.equal(lur, lur2)
+        Lr = torch.tril(lur, -1) + torch.eye(n, dtype=torch.float64, device="cuda")
+        Ur = torch.triu(lur)
+        assert (Lr @ Ur - a[p]).abs().max().item() <= 16 * n * 2.3e-16 * (Lr.abs() @ Ur.abs()).max().item()
 
 
 def test_lookahead_paths_fp32():
