@@ -54,6 +54,136 @@ def spd(rng, n, dtype=np.float64):
     return np.asarray(a @ a.T + n * np.eye(n), dtype=dtype, order="F")
 
 
+# ---- bit patterns (NaN payloads and signed zeros compare as what they are)
+def bits(t):
+    """the elements of a torch tensor or numpy array as integers of the same width"""
+    if isinstance(t, np.ndarray):
+        return t.view(np.int64 if t.dtype == np.float64 else np.int32)
+    import torch
+
+    return t.view(torch.int64 if t.dtype == torch.float64 else torch.int32)
+
+
+def same_bits(x, y):
+    import torch
+
+    return torch.equal(bits(x.contiguous()), bits(y.contiguous()))
+
+
+# ---- padded and offset views inside a guarded parent (the forms faer hands device matrices over in)
+LAYOUTS = ("mat", "sub", "odd", "rowpad", "step2")
+# quiet NaNs with a payload no computation produces; built from integers and compared through integer views only
+GUARD_BITS = {8: 0x7FF8DEADBEEF0BAD, 4: 0x7FC0BEEF}
+
+
+def guard_fill(dtype):
+    dt = np.dtype(dtype)
+    return np.array([GUARD_BITS[dt.itemsize]], dtype=np.int64 if dt.itemsize == 8 else np.int32).view(dt)[0]
+
+
+class ViewBox:
+    """where a view sits in its parent, all in elements: the parent is a `shape` array with element strides `pstrides`, stored
+    `base` elements into its allocation; view (i, j) is parent (r0 + i * rstep, c0 + j)"""
+
+    def __init__(self, nrows, ncols, layout, isz):
+        self.nrows, self.ncols, self.layout, self.rstep, self.base = nrows, ncols, layout, 1, 0
+        if layout == "mat":  # faer::Mat: columns padded to 64 bytes, the allocation itself aligned
+            ld = -(-max(nrows, 1) // (64 // isz)) * (64 // isz)
+            self.r0, self.c0, self.shape, self.pstrides = 0, 0, (ld, ncols + 2), (1, ld)
+        elif layout == "sub":  # a block of a bigger column-major matrix, which itself starts one element into its allocation
+            ld = 2 * nrows + 5  # (row 5, column 3 of such a parent alone is an even element offset: 16-byte aligned in fp64)
+            self.r0, self.c0, self.shape, self.pstrides, self.base = 5, 3, (ld, ncols + 5), (1, ld), 1
+        elif layout == "odd":  # odd column stride: every column aligned to one element only
+            ld = nrows + 3 + (nrows % 2)
+            self.r0, self.c0, self.shape, self.pstrides = 1, 2, (ld, ncols + 4), (1, ld)
+        elif layout == "rowpad":  # row-major parent with padded rows
+            ld = ncols + 3
+            self.r0, self.c0, self.shape, self.pstrides = 2, 1, (nrows + 4, ld), (ld, 1)
+        elif layout == "step2":  # every second row of a column-major parent: both strides non-unit
+            ld = 2 * (nrows + 4)
+            self.r0, self.c0, self.shape, self.pstrides, self.rstep = 1, 1, (ld, ncols + 2), (1, ld), 2
+        else:
+            raise ValueError(layout)
+        self.row_stride, self.col_stride = self.pstrides[0] * self.rstep, self.pstrides[1]
+        self.numel = self.shape[0] * self.shape[1]  # the parent is dense in its own order
+
+    def rows(self):
+        return slice(self.r0, self.r0 + self.rstep * self.nrows, self.rstep)
+
+    def cols(self):
+        return slice(self.c0, self.c0 + self.ncols)
+
+    def view_mask(self):
+        m = np.zeros(self.shape, bool)
+        m[self.rows(), self.cols()] = True
+        return m
+
+
+def view_box(shape, layout, dtype):
+    return ViewBox(shape[0], shape[1], layout, np.dtype(dtype).itemsize)
+
+
+def _place_flat(a, layout, fill):
+    a = np.asarray(a)
+    assert a.ndim == 2 and a.dtype in (np.float64, np.float32)
+    box = view_box(a.shape, layout, a.dtype)
+    flat = np.empty(box.base + box.numel, dtype=a.dtype)
+    flat[:] = guard_fill(a.dtype) if fill is None else fill
+    parent = np.lib.stride_tricks.as_strided(flat[box.base:], box.shape, tuple(s * a.itemsize for s in box.pstrides))
+    parent[box.rows(), box.cols()] = a
+    return box, flat, parent
+
+
+def place_host(a, layout, fill=None):
+    """(parent, view) as numpy arrays: `view` holds the values of `a` with the element strides of `layout`, every other element
+    of `parent` is `fill` (default: the guard NaN)"""
+    box, _, parent = _place_flat(a, layout, fill)
+    return parent, parent[box.rows(), box.cols()]
+
+
+def place(a, layout, fill=None):
+    """place_host on the device: (parent, view) as torch cuda tensors with the same element strides"""
+    import torch
+
+    box, flat, _ = _place_flat(a, layout, fill)
+    dev = torch.from_numpy(bits(flat)).cuda().view(torch.float64 if flat.dtype == np.float64 else torch.float32)
+    parent = dev.as_strided(box.shape, box.pstrides, box.base)
+    return parent, parent[box.rows(), box.cols()]
+
+
+def _host_bits(t):
+    return np.array(bits(t) if isinstance(t, np.ndarray) else bits(t).cpu().numpy())
+
+
+def guard_intact(parent, parent0, box, what=""):
+    """every element of `parent` outside the view has the bit pattern it has in the snapshot `parent0`; otherwise an
+    AssertionError names the first changed coordinates relative to the view and the kind of padding they lie in"""
+    now, was = _host_bits(parent), _host_bits(parent0)
+    assert now.shape == was.shape == tuple(box.shape)
+    bad = np.argwhere((now != was) & ~box.view_mask())
+    if len(bad) == 0:
+        return
+    lines = []
+    for pr, pc in bad[:8]:
+        i, rem = divmod(int(pr) - box.r0, box.rstep)
+        j = int(pc) - box.c0
+        if j >= box.ncols:
+            where = "beyond the last column"
+        elif j < 0:
+            where = "before the first column"
+        elif i >= box.nrows:
+            where = "in the padding below a column"
+        elif i < 0:
+            where = "in the padding above a column"
+        else:
+            assert rem != 0
+            where = "between two rows of the view"
+        row = f"{i}" if rem == 0 else f"{i}+{rem}/{box.rstep}"
+        lines.append(f"(row {row}, column {j}) {where}: {int(was[pr, pc]):#x} -> {int(now[pr, pc]):#x}")
+    raise AssertionError(f"{what} layout {box.layout}: {len(bad)} element(s) outside the {box.nrows} x {box.ncols} view changed; first: "
+                         + "; ".join(lines))
+
+
 # ---- route counters of the GEMM / TRSM dispatch (faer_hip_debug_route_counts)
 def route_names():
     """FaerHipRoute_* in enum order, read from the header (like test_cabi.py reads the exports)"""

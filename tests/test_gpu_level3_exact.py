@@ -19,7 +19,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-from gpu_util import ROOT, ROUTES, Routes, init_gpu
+from gpu_util import ROOT, ROUTES, Routes, bits, init_gpu, same_bits
 
 F32, F64 = np.float32, np.float64
 DTYPES = [F64, F32]
@@ -103,18 +103,6 @@ def ints(g, shape, r, dtype, order="F", device="cuda"):
     else:
         t = torch.randint(-r, r + 1, (rows, cols), generator=g, device=device, dtype=torch.int64).to(tdt)
     return t
-
-
-def bits(t):
-    import torch
-
-    return t.view(torch.int64 if t.dtype == torch.float64 else torch.int32)
-
-
-def same_bits(x, y):
-    import torch
-
-    return torch.equal(bits(x.contiguous()), bits(y.contiguous()))
 
 
 def tdtype(dtype):
