@@ -122,6 +122,25 @@ class EvdStatus(C.Structure):
 EVD_OK, EVD_NO_CONVERGENCE = 0, 1
 
 
+class BidiagParams(C.Structure):
+    _fields_ = [("par_threshold", C.c_size_t)]
+
+
+class SvdParams(C.Structure):
+    """include/faer_hip.h FaerSvdParams {bidiag: {par_threshold}, qr: {blocking_threshold, par_threshold},
+    recursion_threshold, qr_ratio_threshold}"""
+    _fields_ = [("bidiag", BidiagParams), ("qr", QrParams), ("recursion_threshold", C.c_size_t),
+                ("qr_ratio_threshold", C.c_double)]
+
+
+class SvdStatus(C.Structure):
+    """include/faer_hip.h FaerSvdStatus: tag (0 Ok, 1 NoConvergence), then a union of one size_t"""
+    _fields_ = [("tag", C.c_int), ("padding", C.c_size_t)]
+
+
+SVD_OK, SVD_NO_CONVERGENCE = 0, 1
+
+
 BCAST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
 
 
@@ -465,6 +484,30 @@ def self_adjoint_evd(a, s, u=None, params=None, par=PAR_SEQ):
     fn = getattr(L, f"libfaer_v0_23_self_adjoint_evd_{suf}")
     fn.restype = EvdStatus
     st = fn(_mat(a), um, sv, par, MemAlloc(None, 0), params)
+    return st.tag
+
+
+def svd(a, s, u=None, v=None, params=None, par=PAR_SEQ):
+    """faer::linalg::svd::svd (svd/mod.rs:530): singular values of `a` (m x n, never written) in nonincreasing order into
+    the 1-D `s` (min(m, n) entries); with `u` (m x min(m, n) or m x m) / `v` (n x min(m, n) or n x n) the left / right
+    singular vectors, a = u[:, :k] diag(s) v[:, :k]^T.  Returns the status tag (SVD_OK or SVD_NO_CONVERGENCE)."""
+    suf, _, _ = _dtype_suffix(a)
+    L = lib()
+    if params is None:
+        pf = getattr(L, f"libfaer_v0_23_SvdParams_{suf}")
+        pf.restype = SvdParams
+        params = pf()
+    if _is_torch(s):
+        assert s.dim() == 1
+        sv = VecRef(s.data_ptr(), s.shape[0], s.stride(0))
+    else:
+        assert s.ndim == 1
+        sv = VecRef(s.ctypes.data, s.shape[0], s.strides[0] // s.itemsize)
+    um = _mat(u, MatMut) if u is not None else MatMut(None, a.shape[0], 0, 1, a.shape[0])
+    vm = _mat(v, MatMut) if v is not None else MatMut(None, a.shape[1], 0, 1, a.shape[1])
+    fn = getattr(L, f"libfaer_v0_23_svd_{suf}")
+    fn.restype = SvdStatus
+    st = fn(_mat(a), um, sv, vm, par, MemAlloc(None, 0), params)
     return st.tag
 
 

@@ -699,6 +699,47 @@ template <typename T> FaerEvdStatus self_adjoint_evd_api(FaerMatRef A, FaerMatMu
 	return st;
 }
 
+// svd/mod.rs:530-671 behind lib.rs:2327-2366 (U.ncols == 0 / V.ncols == 0: no left / right vectors)
+template <typename T> FaerSvdStatus svd_api(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerMatMut V, FaerSvdParams params)
+{
+	const size_t m = A.nrows, n = A.ncols, size = m < n ? m : n;
+	FH_CHECK(S.len == size, "svd: S must have min(nrows, ncols) entries"); // mod.rs:542
+	FH_CHECK(U.ncols == 0 || (U.nrows == m && (U.ncols == m || U.ncols == size)), "svd: U must be nrows x min(nrows, ncols) or nrows x nrows");
+	FH_CHECK(V.ncols == 0 || (V.nrows == n && (V.ncols == n || V.ncols == size)), "svd: V must be ncols x min(nrows, ncols) or ncols x ncols");
+	FaerSvdStatus st;
+	memset(&st, 0, sizeof(st));
+	st.tag = FaerSvdStatus_Ok;
+	if (size == 0) {
+		// mod.rs:586-591: the left factor of the (transposed) problem is the identity pattern, the other one has no entries
+		FaerMatMut I = n > m ? V : U;
+		if (I.ncols > 0 && I.nrows > 0) {
+			Staged<T> e(view<T>(I), false, true);
+			svd_identity_dev<T>(e.dev);
+			ctx().sync();
+		}
+		return st;
+	}
+	int r;
+	{
+		Staged<const T> a(view<T>(A), true, false);
+		FaerMatMut Sm{S.ptr, S.len, 1, S.stride, 0};
+		Staged<T> s(view<T>(Sm), false, true);
+		FaerMatMut none{nullptr, 0, 0, 0, 0};
+		Staged<T> u(view<T>(U.ncols ? U : none), false, true), v(view<T>(V.ncols ? V : none), false, true);
+		MatV<T> ud = u.dev, vd = v.dev;
+		if (U.ncols == 0)
+			ud = MatV<T>{nullptr, (idx_t) m, 0, 1, (idx_t) m};
+		if (V.ncols == 0)
+			vd = MatV<T>{nullptr, (idx_t) n, 0, 1, (idx_t) n};
+		const size_t big = m < n ? n : m;
+		r = svd_dev<T>(a.dev, ud, vd, s.dev.p, s.dev.rs, svd_leaf_size(params.recursion_threshold), params.qr_ratio_threshold,
+			       (idx_t) params.qr.blocking_threshold, (idx_t) qr_block_size(big, size), (idx_t) qr_block_size(size, size));
+	}
+	if (r != 0)
+		st.tag = FaerSvdStatus_NoConvergence;
+	return st;
+}
+
 } // namespace
 
 extern "C" {
@@ -1447,6 +1488,34 @@ void faer_hip_debug_dump_timing(void)
 		(void) par;                                                                                            \
 		(void) mem;                                                                                            \
 		return self_adjoint_evd_api<T>(A, U, S, params);                                                       \
+	}
+FH_FOR_DTYPES(X)
+#undef X
+
+#define X(suf, T)                                                                                                      \
+	FaerBidiagParams libfaer_v0_23_BidiagParams_##suf(void) { return FaerBidiagParams{192 * 256}; }                 \
+	FaerSvdParams libfaer_v0_23_SvdParams_##suf(void)                                                              \
+	{                                                                                                              \
+		return FaerSvdParams{FaerBidiagParams{192 * 256}, libfaer_v0_23_QrParams_##suf(), 128, 11.0 / 6.0};     \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_svd_scratch_##suf(size_t nrows, size_t ncols, FaerComputeSvdVectors compute_U,        \
+						   FaerComputeSvdVectors compute_V, FaerPar par, FaerSvdParams params)  \
+	{                                                                                                              \
+		(void) compute_U;                                                                                      \
+		(void) compute_V;                                                                                      \
+		(void) par;                                                                                            \
+		(void) params;                                                                                         \
+		const size_t big = nrows < ncols ? ncols : nrows, small = nrows < ncols ? nrows : ncols;               \
+		if (small == 0)                                                                                        \
+			return layout(0, 1); /* StackReq::EMPTY (mod.rs:483-485) */                                    \
+		return layout((2 * big * small + 8 * (small + 1) * (small + 1) + 64 * (small + 1)) * sizeof(T), 64);   \
+	}                                                                                                              \
+	FaerSvdStatus libfaer_v0_23_svd_##suf(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerMatMut V, FaerPar par,     \
+					      FaerMemAlloc mem, FaerSvdParams params)                                   \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) mem;                                                                                            \
+		return svd_api<T>(A, U, S, V, params);                                                                 \
 	}
 FH_FOR_DTYPES(X)
 #undef X

@@ -430,6 +430,17 @@ void apply_householder_sequence_left_dev(MatV<const T> V, MatV<const T> H, MatV<
 // for NoConvergence (a non-finite tridiagonal or a leaf over its iteration cap).
 idx_t evd_leaf_size(size_t recursion_threshold);
 template <typename T> int self_adjoint_evd_dev(MatV<const T> A, MatV<T> U, T *S, idx_t ss, idx_t leaf, idx_t bs);
+// svd/mod.rs:530 svd (svd.hip): S (min(m, n) entries, stride ss, device) <- nonincreasing singular values of A (m x n, never
+// written), U (m x min(m, n) or m x m) / V (n x min(m, n) or n x n) <- singular vectors unless their .p == nullptr.  A wide
+// matrix runs as its transpose with U and V swapped; a tall one with m / n > qr_ratio_threshold goes through geqrf_dev first.
+// Leaves of the bidiagonal divide and conquer have at most `leaf` entries (svd_leaf_size); bs_mn / bs_nn: block sizes of the
+// Householder factors of the max(m, n) x min(m, n) reduction and of the square one behind the QR pre-step.  Returns 0, or 1
+// for NoConvergence (a non-finite bidiagonal form or a leaf over its iteration cap).
+idx_t svd_leaf_size(size_t recursion_threshold);
+template <typename T> void svd_identity_dev(MatV<T> X); // zero, ones on the diagonal (mod.rs:586-591)
+template <typename T>
+int svd_dev(MatV<const T> A, MatV<T> U, MatV<T> V, T *S, idx_t ss, idx_t leaf, double qr_ratio_threshold, idx_t qr_blocking_threshold,
+	    idx_t bs_mn, idx_t bs_nn);
 
 // small utility kernels (util.hip)
 template <typename T> void fill_dev(MatV<T> A, DstKind kind, T value);

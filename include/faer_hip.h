@@ -131,6 +131,18 @@ typedef struct FaerEvdStatus {
 		struct { size_t padding; } no_convergence;
 	};
 } FaerEvdStatus;
+/* SVD: faer.h:87-99, :196-201, :471-490, lib.rs:2327-2366 (svd/mod.rs:22-56, svd/bidiag.rs) */
+typedef enum FaerComputeSvdVectors { FaerComputeSvdVectors_No = 0, FaerComputeSvdVectors_Thin = 1, FaerComputeSvdVectors_Full = 2 } FaerComputeSvdVectors;
+typedef struct FaerBidiagParams { size_t par_threshold; } FaerBidiagParams;
+typedef struct FaerSvdParams { FaerBidiagParams bidiag; FaerQrParams qr; size_t recursion_threshold; double qr_ratio_threshold; } FaerSvdParams;
+typedef enum FaerSvdStatus_Tag { FaerSvdStatus_Ok = 0, FaerSvdStatus_NoConvergence = 1 } FaerSvdStatus_Tag;
+typedef struct FaerSvdStatus {
+	FaerSvdStatus_Tag tag;
+	union {
+		struct { size_t padding; } ok;
+		struct { size_t padding; } no_convergence;
+	};
+} FaerSvdStatus;
 /* faer-ffi/src/lib.rs:796-801; pointers to a real scalar of the matrix dtype (HOST memory), NULL == 0 */
 typedef struct FaerLltRegularization { const void *dynamic_regularization_delta; const void *dynamic_regularization_epsilon; } FaerLltRegularization;
 /* lib.rs:820-828: signs is a slice of i8 (HOST memory, `dim` entries) or a null ptr */
@@ -474,6 +486,27 @@ FAER_HIP_API FaerLayout libfaer_v0_23_self_adjoint_evd_scratch_f64(size_t dim, F
 FAER_HIP_API FaerLayout libfaer_v0_23_self_adjoint_evd_scratch_f32(size_t dim, FaerComputeEigenvectors compute_U, FaerPar par, FaerSelfAdjointEvdParams params);
 FAER_HIP_API FaerEvdStatus libfaer_v0_23_self_adjoint_evd_f64(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerPar par, FaerMemAlloc mem, FaerSelfAdjointEvdParams params);
 FAER_HIP_API FaerEvdStatus libfaer_v0_23_self_adjoint_evd_f32(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerPar par, FaerMemAlloc mem, FaerSelfAdjointEvdParams params);
+/* ---------------------------------------------------------------------------------------------
+ * 2f. Singular value decomposition (faer-ffi/src/lib.rs:2327-2366; svd/mod.rs:530-671): A = U[:, :k] diag(S) V[:, :k]^T,
+ *     k = min(nrows, ncols).  A (m x n) is never written.  S (k entries) receives the singular values, nonnegative and
+ *     nonincreasing.  U.ncols == 0: no left vectors; otherwise U is m x k (thin) or m x m (full).  V.ncols == 0: no right
+ *     vectors; otherwise V is n x k or n x n.  k == 0: S is empty and a requested m x m U (n x n V for m == 0) receives
+ *     the identity.  A wide matrix runs as its transpose; a tall one with m / n > qr_ratio_threshold goes through a QR
+ *     factorization first.  Bidiagonalization (csrc/condense.hip), divide and conquer on the bidiagonal with
+ *     QR-iteration leaves (csrc/svd.hip), two block Householder back-transforms.  Leaves hold at most
+ *     min(max(recursion_threshold, 4), 64) entries: a larger threshold is clamped to 64.  par, mem, params.bidiag and
+ *     params.qr.par_threshold are accepted and ignored.  NoConvergence: a non-finite entry in the bidiagonal form, or a
+ *     leaf over the reference's iteration cap.  Host or device operands, any strides; only the addressed elements are
+ *     written.  The scratch query needs no device.
+ * --------------------------------------------------------------------------------------------- */
+FAER_HIP_API FaerBidiagParams libfaer_v0_23_BidiagParams_f64(void);
+FAER_HIP_API FaerBidiagParams libfaer_v0_23_BidiagParams_f32(void);
+FAER_HIP_API FaerSvdParams libfaer_v0_23_SvdParams_f64(void);
+FAER_HIP_API FaerSvdParams libfaer_v0_23_SvdParams_f32(void);
+FAER_HIP_API FaerLayout libfaer_v0_23_svd_scratch_f64(size_t nrows, size_t ncols, FaerComputeSvdVectors compute_U, FaerComputeSvdVectors compute_V, FaerPar par, FaerSvdParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_svd_scratch_f32(size_t nrows, size_t ncols, FaerComputeSvdVectors compute_U, FaerComputeSvdVectors compute_V, FaerPar par, FaerSvdParams params);
+FAER_HIP_API FaerSvdStatus libfaer_v0_23_svd_f64(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerMatMut V, FaerPar par, FaerMemAlloc mem, FaerSvdParams params);
+FAER_HIP_API FaerSvdStatus libfaer_v0_23_svd_f32(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerMatMut V, FaerPar par, FaerMemAlloc mem, FaerSvdParams params);
 
 #endif /* FAER_HIP_NO_FFI_PROTOTYPES */
 
