@@ -121,6 +121,20 @@ struct Ctx {
 	void quiesce();
 };
 Ctx &ctx();
+
+// Raises Kernel's dynamic LDS limit once per DEVICE and kernel: the attribute belongs to the device that is current at the
+// time of the call, and a thread bound to a second GPU must not launch without it (atomic flags: several threads; a device
+// number past the 64 bits sets it on every call).
+template <auto Kernel> inline void raise_dynamic_lds(size_t bytes)
+{
+	static std::atomic<unsigned long long> attr_done{0}; // bit d: device d
+	const int dev = ctx().device;
+	const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
+	if (bit == 0 || !(attr_done.load(std::memory_order_acquire) & bit)) {
+		FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes));
+		attr_done.fetch_or(bit, std::memory_order_release);
+	}
+}
 void debug_stream_xcc(int which, int nblocks, unsigned *out_host); // which: 0 caller's stream, 1 bulk, 2 panel
 void prof_collect(double *out, double *spans = nullptr, size_t cap = 0, size_t *nspans = nullptr); // Ctx::PROF_CLASSES x {ms, launches, units} of the spans recorded since prof_on; optionally one record of 8 doubles per span (ctx.hip)
 double xwg_hop_us(int iters); // idle-chip hand-off latency between two workgroups, microseconds (ctx.hip)

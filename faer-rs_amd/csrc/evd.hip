@@ -7,9 +7,10 @@
 // The tridiagonal solve follows the reference's recursion (split at n / 2, rank-one tear d[n1-1] -= |rho|, d[n1] -= |rho|)
 // but runs it level by level, bottom up; every launch covers all nodes of one level:
 //   * evd_leaf_kernel: implicit symmetric QR with the Wilkinson shift (tridiag_evd.rs:9-190) on every leaf of at most
-//     min(max(recursion_threshold, 4), 64) rows (evd_leaf_size; the kernel holds up to 128), one single-wave workgroup per
-//     leaf, the leaf's eigenvector block in LDS (128 x 129 fp64 = 129 KiB at most).  Lane 0 generates a sweep's Givens rotations; then every lane applies the whole sweep
-//     to its rows of U (rotations on the right act on each row on its own: one barrier per sweep).
+//     min(max(recursion_threshold, 4), 64) rows (evd_leaf_size), one single-wave workgroup per leaf, one row per lane, the
+//     leaf's eigenvector block in LDS (64 x 65 fp64 = 32.5 KiB at most).  Lane 0 generates a sweep's Givens rotations; then
+//     every lane applies the whole sweep to its row of U (rotations on the right act on each row on its own: one barrier
+//     per sweep).
 //   * evd_merge_prep_kernel (one workgroup per merge): z from the last row of U0 and the first row of U1, the merge of
 //     the two ascending halves (pl_before), deflation of small rho z_i and of runs of nearly equal d (Householder
 //     reflector as the reference), compaction of the k non-deflated entries (:370-480).
@@ -25,7 +26,7 @@
 #include <cmath>
 
 #include "common.h"
-#include "secular.h"
+#include "dnc.h"
 
 namespace fh {
 
@@ -40,102 +41,6 @@ template <typename T> struct EvdWork {
 	T *rho;
 };
 
-// ---- input --------------------------------------------------------------------------------------
-template <typename T> struct EvdBits;
-template <> struct EvdBits<double> {
-	typedef unsigned long long U;
-	static __device__ U of(double x) { return (U) __double_as_longlong(x); }
-	static __device__ double val(U u) { return __longlong_as_double((long long) u); }
-	static constexpr double rmin = 1.0010415475915505e-146, rmax = 9.989595361011175e+145; // sqrt(sml / eps), 1 / rmin
-};
-template <> struct EvdBits<float> {
-	typedef unsigned int U;
-	static __device__ U of(float x) { return __float_as_uint(x); }
-	static __device__ float val(U u) { return __uint_as_float(u); }
-	static constexpr float rmin = 3.1401849e-16f, rmax = 3.1845258e+15f;
-};
-
-// trid <- lower(A) (mod.rs:327 copy_from_triangular_lower), zero above the diagonal: the strict upper triangle of A is never
-// read.  Also max |lower(A)| (the bits of a non-negative float order like unsigned integers): one atomic per block.
-template <typename T> __global__ __launch_bounds__(256) void evd_copy_lower_kernel(const T *A, idx_t rs, idx_t cs, T *X, idx_t n,
-										   typename EvdBits<T>::U *amax)
-{
-	__shared__ T red[4];
-	const idx_t t = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	T v = 0;
-	if (t < n * n) {
-		const idx_t i = t % n, j = t / n;
-		v = i >= j ? A[i * rs + j * cs] : (T) 0;
-		X[t] = v;
-	}
-	const T m = block_reduce<T, true>(ev_abs(v), red);
-	if (threadIdx.x == 0)
-		atomicMax(amax, EvdBits<T>::of(m));
-}
-
-// the scaling of LAPACK's xSYEV: a matrix whose largest entry lies outside [rmin, rmax] is scaled by a power of two into that
-// range (exact), the eigenvalues are scaled back at the end; fac[0] <- the factor (1 inside the range)
-template <typename T> __global__ void evd_scale_kernel(T *X, idx_t nn, const typename EvdBits<T>::U *amax, T *fac)
-{
-	const T a = EvdBits<T>::val(*amax);
-	int e = 0;
-	if (isfinite(a) && a > (T) 0) {
-		if (a > EvdBits<T>::rmax)
-			e = ilogb((double) EvdBits<T>::rmax) - ilogb((double) a) - 1;
-		else if (a < EvdBits<T>::rmin)
-			e = ilogb((double) EvdBits<T>::rmin) - ilogb((double) a) + 1;
-	}
-	if (e == 0) {
-		if (blockIdx.x == 0 && threadIdx.x == 0)
-			fac[0] = 1;
-		return;
-	}
-	const T f = (T) ldexp(1.0, e);
-	const idx_t t = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if (t < nn)
-		X[t] *= f;
-	if (t == 0)
-		fac[0] = f;
-}
-
-// diag / offdiag of the tridiagonal T (mod.rs:345-356) and max(|d|, |e|); any non-finite entry sets the status before any iteration
-template <typename T>
-__global__ __launch_bounds__(256) void evd_extract_kernel(const T *X, idx_t n, T *D, T *E, typename EvdBits<T>::U *tmax, int *status)
-{
-	__shared__ T red[4];
-	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	T m = 0;
-	if (i < n) {
-		const T d = X[i + i * n];
-		const T e = i + 1 < n ? X[i + 1 + i * n] : (T) 0;
-		D[i] = d;
-		E[i] = e;
-		if (!isfinite(d) || !isfinite(e))
-			status[0] = 1;
-		m = ev_max(ev_abs(d), ev_abs(e));
-	}
-	m = block_reduce<T, true>(m, red);
-	if (threadIdx.x == 0)
-		atomicMax(tmax, EvdBits<T>::of(m));
-}
-
-// The root finder's stopping tests compare secular-function values with eps in absolute terms (bidiag_svd.rs:64-66), so
-// the solve is not scale invariant: the tridiagonal is scaled by a power of two (exact) to max(|d|, |e|) in [1, 2).
-// tfac[0] <- the factor.
-template <typename T> __global__ void evd_tscale_kernel(T *D, T *E, idx_t n, const typename EvdBits<T>::U *tmax, T *tfac)
-{
-	const T a = EvdBits<T>::val(*tmax);
-	const int e = isfinite(a) && a > (T) 0 ? -ilogb((double) a) : 0;
-	const T f = (T) ldexp(1.0, e);
-	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) {
-		D[i] *= f;
-		E[i] *= f;
-	}
-	if (i == 0)
-		tfac[0] = f;
-}
-
 // rank-one tears of every merge (tridiag_evd.rs:290-296).  With leaves of at least 4 rows no two merges touch the same entry.
 template <typename T> __global__ void evd_tear_kernel(const int *merges, int count, T *D, const T *E, const int *status)
 {
@@ -149,20 +54,14 @@ template <typename T> __global__ void evd_tear_kernel(const int *merges, int cou
 }
 
 // ---- leaves: QR algorithm -----------------------------------------------------------------------
-constexpr int EVD_LEAF_MAX = 128;
+constexpr int EVD_LEAF_MAX = 64; // one row per lane
 
-// highest index < lim whose bit is set in the 128-bit mask (lo: indices 0..63, hi: 64..127), -1 if none
-__device__ __forceinline__ int highest_below(unsigned long long lo, unsigned long long hi, int lim)
+// highest index < lim whose bit is set in the mask, -1 if none
+__device__ __forceinline__ int highest_below(unsigned long long mask, int lim)
 {
-	if (lim > 64) {
-		const unsigned long long h = lim >= 128 ? hi : hi & ((1ull << (lim - 64)) - 1ull);
-		if (h)
-			return 127 - __clzll((long long) h);
-		lim = 64;
-	}
 	if (lim <= 0)
 		return -1;
-	const unsigned long long l = lim >= 64 ? lo : lo & ((1ull << lim) - 1ull);
+	const unsigned long long l = lim >= 64 ? mask : mask & ((1ull << lim) - 1ull);
 	return l ? 63 - __clzll((long long) l) : -1;
 }
 
@@ -182,11 +81,11 @@ __global__ __launch_bounds__(64) void evd_leaf_kernel(const int *leaves, T *D, c
 	if (status[0])
 		return;
 	const int ld = m + 1;
-	T *u = reinterpret_cast<T *>(evd_lds); // row major, u[i * ld + j] = U(i, j): lane i owns rows i and i + 64
+	T *u = reinterpret_cast<T *>(evd_lds); // row major, u[i * ld + j] = U(i, j): lane i owns row i
 	T *d = u + (size_t) m * ld, *e = d + EVD_LEAF_MAX, *rc = e + EVD_LEAF_MAX, *rsn = rc + EVD_LEAF_MAX;
 	int *perm = reinterpret_cast<int *>(rsn + EVD_LEAF_MAX);
 	__shared__ int sh_kend;
-	const T eps = EvdTraits<T>::eps, sml = EvdTraits<T>::sml;
+	const T eps = DncTraits<T>::eps, sml = DncTraits<T>::sml;
 
 	for (int t = tid; t < m * ld; t += 64)
 		u[t] = (t % ld) == (t / ld) ? (T) 1 : (T) 0;
@@ -260,7 +159,7 @@ __global__ __launch_bounds__(64) void evd_leaf_kernel(const int *leaves, T *D, c
 			}
 			__syncthreads();
 			int start = 0, end = m - 1;
-			const long max_iters = EvdTraits<T>::iter_factor * (long) m * (long) m;
+			const long max_iters = DncTraits<T>::iter_factor * (long) m * (long) m;
 			for (long iter = 0; iter < max_iters; ++iter) {
 				for (int i = start + tid; i < end; i += 64) {
 					const T ei = ev_abs(e[i]);
@@ -268,18 +167,17 @@ __global__ __launch_bounds__(64) void evd_leaf_kernel(const int *leaves, T *D, c
 						e[i] = 0;
 				}
 				__syncthreads();
-				const bool v0 = tid < m - 1, v1 = tid + 64 < m - 1;
-				const T e0 = v0 ? e[tid] : (T) 0, e1 = v1 ? e[tid + 64] : (T) 0;
-				const unsigned long long nz0 = __ballot(v0 && e0 != (T) 0), nz1 = __ballot(v1 && e1 != (T) 0);
-				const unsigned long long z0 = __ballot(v0 && e0 == (T) 0), z1 = __ballot(v1 && e1 == (T) 0);
-				end = highest_below(nz0, nz1, end) + 1; // while end > 0 && offdiag[end - 1] == 0: end -= 1
+				const bool v0 = tid < m - 1;
+				const T e0 = v0 ? e[tid] : (T) 0;
+				const unsigned long long nz0 = __ballot(v0 && e0 != (T) 0), z0 = __ballot(v0 && e0 == (T) 0);
+				end = highest_below(nz0, end) + 1; // while end > 0 && offdiag[end - 1] == 0: end -= 1
 				if (end == 0)
 					break;
 				if (iter + 1 == max_iters) {
 					fail = true;
 					break;
 				}
-				start = highest_below(z0, z1, end - 1) + 1; // while start > 0 && offdiag[start - 1] != 0: start -= 1
+				start = highest_below(z0, end - 1) + 1; // while start > 0 && offdiag[start - 1] != 0: start -= 1
 				if (tid == 0) {
 					const T td = (d[end - 1] - d[end]) * (T) 0.5;
 					const T ee = e[end - 1];
@@ -329,17 +227,8 @@ __global__ __launch_bounds__(64) void evd_leaf_kernel(const int *leaves, T *D, c
 				}
 				__syncthreads();
 				const int kend = sh_kend;
-				for (int i = tid; i < m; i += 64) {
-					// apply_on_the_right_in_place on columns (k + 1, k): U(:, k+1) = c a + s b, U(:, k) = c b - s a
-					T *row = u + (size_t) i * ld;
-					T x = row[start];
-					for (int k = start; k < kend; ++k) {
-						const T a = row[k + 1], c = rc[k], s = rsn[k];
-						row[k] = c * x - s * a;
-						x = c * a + s * x;
-					}
-					row[kend] = x;
-				}
+				for (int i = tid; i < m; i += 64)
+					rot_chain_forward(u + (size_t) i * ld, start, kend, rc, rsn);
 				__syncthreads();
 			}
 			if (!fail && tid == 0) {
@@ -392,7 +281,7 @@ __global__ __launch_bounds__(256) void evd_merge_prep_kernel(const int *merges, 
 	const int b = blockIdx.x, tid = threadIdx.x;
 	const idx_t off = merges[3 * b];
 	const int n = merges[3 * b + 1], n1 = merges[3 * b + 2], n2 = n - n1;
-	const T eps = EvdTraits<T>::eps, sml = EvdTraits<T>::sml;
+	const T eps = DncTraits<T>::eps, sml = DncTraits<T>::sml;
 	const T rho_in = E[off + n1 - 1];
 	const bool neg = rho_in < (T) 0;
 	const T inv_sqrt2 = ev_sqrt((T) 0.5);
@@ -683,45 +572,12 @@ template <typename T> __global__ __launch_bounds__(256) void evd_qhat_kernel(con
 	}
 }
 
-template <typename T> __global__ void evd_write_s_kernel(const T *D, idx_t n, T *S, idx_t ss, const T *fac) // fac: {A scale, T scale}
-{
-	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n)
-		S[i * ss] = D[i] * ((T) 1 / fac[0]) * ((T) 1 / fac[1]);
-}
-
-struct EvdNode {
-	idx_t off, n;
-	int depth;
-};
-
-void evd_plan(idx_t off, idx_t n, int depth, idx_t leaf, std::vector<EvdNode> &leaves, std::vector<std::vector<EvdNode>> &merges)
-{
-	if (n <= leaf) {
-		leaves.push_back(EvdNode{off, n, depth});
-		return;
-	}
-	if ((int) merges.size() <= depth)
-		merges.resize((size_t) depth + 1);
-	merges[(size_t) depth].push_back(EvdNode{off, n, depth});
-	const idx_t n1 = n / 2;
-	evd_plan(off, n1, depth + 1, leaf, leaves, merges);
-	evd_plan(off + n1, n - n1, depth + 1, leaf, leaves, merges);
-}
-
-inline unsigned blocks_for(idx_t count, int per) { return (unsigned) ((count + per - 1) / per); }
-
 } // namespace
 
-// Leaves of min(max(recursion_threshold, 4), 64) rows.  The leaf kernel holds up to EVD_LEAF_MAX = 128 rows, but lane 0's
-// Givens chain grows as the square of the leaf size while the merge level that 64-row leaves add is cheap: at N = 4096 fp64
-// the solve takes 8.8 ms with 64-row leaves against 15.8 ms with 128-row ones (32: 8.6).
-constexpr size_t EVD_LEAF_CLAMP = 64;
-idx_t evd_leaf_size(size_t recursion_threshold)
-{
-	const size_t t = recursion_threshold < 4 ? 4 : recursion_threshold;
-	return (idx_t) (t > EVD_LEAF_CLAMP ? EVD_LEAF_CLAMP : t);
-}
+// Leaves of min(max(recursion_threshold, 4), 64) rows, the most evd_leaf_kernel holds.  Lane 0's Givens chain grows as the
+// square of the leaf size while the merge level that smaller leaves add is cheap: at N = 4096 fp64 the solve took 8.8 ms
+// with 64-row leaves against 15.8 ms with the 128-row ones an earlier leaf kernel could hold (32: 8.6).
+idx_t evd_leaf_size(size_t recursion_threshold) { return dnc_leaf_size(recursion_threshold, EVD_LEAF_MAX); }
 
 template <typename T> int self_adjoint_evd_dev(MatV<const T> A, MatV<T> U, T *S, idx_t ss, idx_t leaf, idx_t bs)
 {
@@ -733,98 +589,58 @@ template <typename T> int self_adjoint_evd_dev(MatV<const T> A, MatV<T> U, T *S,
 	const bool want_u = U.p != nullptr;
 
 	// plan of the recursion (host, from n alone)
-	std::vector<EvdNode> leaves;
-	std::vector<std::vector<EvdNode>> merges;
-	evd_plan(0, n, 0, leaf, leaves, merges);
-	const int levels = (int) merges.size();
-	std::vector<int> tab;
-	for (const EvdNode &l : leaves) {
-		tab.push_back((int) l.off);
-		tab.push_back((int) l.n);
-		tab.push_back(l.depth & 1);
-	}
-	std::vector<size_t> level_at((size_t) levels);
-	size_t nmerges = 0, max_level = 0;
-	for (int lv = 0; lv < levels; ++lv) {
-		level_at[(size_t) lv] = tab.size();
-		nmerges += merges[(size_t) lv].size();
-		max_level = std::max(max_level, merges[(size_t) lv].size());
-		for (const EvdNode &m : merges[(size_t) lv]) {
-			tab.push_back((int) m.off);
-			tab.push_back((int) m.n);
-			tab.push_back((int) (m.n / 2));
-		}
-	}
-	FH_CHECK(leaves.size() < (1u << 31) && max_level < 65536, "self_adjoint_evd: too many nodes");
+	const DncPlan plan(n, leaf, 0, "self_adjoint_evd: too many nodes");
+	const int levels = plan.levels();
 
 	// device memory: the reduced matrix, its block factors, two eigenvector buffers (depth parity), Qhat, the work vectors
 	const size_t nn = (size_t) n * (size_t) n;
 	Scratch trid(nn * sizeof(T)), hb((size_t) bs * (size_t) (n > 1 ? n - 1 : 1) * sizeof(T));
 	Scratch ub0(want_u ? 16 : nn * sizeof(T)), ub1(levels > 0 ? nn * sizeof(T) : 16), qb(levels > 0 ? nn * sizeof(T) : 16);
-	Scratch vec((size_t) 12 * (size_t) n * sizeof(T) + (size_t) (4 * n + 2 * (n + 1)) * sizeof(int) + 64), tb(tab.size() * sizeof(int) + 16),
+	Scratch vec((size_t) 12 * (size_t) n * sizeof(T) + (size_t) (4 * n + 2 * (n + 1)) * sizeof(int) + 64), tb(plan.tab_bytes() + 16),
 		stb(16 * sizeof(int));
 	int *status = stb.as<int>();
 	T *D = vec.as<T>(), *E = D + n;
 	EvdWork<T> w;
 	{
 		T *p = E + n;
-		T **tp[] = {&w.z, &w.pd0, &w.pz0, &w.pd, &w.pz, &w.hh, &w.mu, &w.sh, &w.zh, &w.rho};
-		for (T **q : tp) {
-			*q = p;
-			p += n;
-		}
+		dnc_carve(p, n, {&w.z, &w.pd0, &w.pz0, &w.pd, &w.pz, &w.hh, &w.mu, &w.sh, &w.zh, &w.rho});
 		int *ip = reinterpret_cast<int *>(p);
-		int **ipp[] = {&w.plb, &w.pla, &w.rl, &w.pr};
-		for (int **q : ipp) {
-			*q = ip;
-			ip += n;
-		}
+		dnc_carve(ip, n, {&w.plb, &w.pla, &w.rl, &w.pr});
 		w.k = ip;
 		w.applied = ip + (n + 1);
 	}
 	int *tab_dev = tb.as<int>();
 	FH_HIP(hipMemsetAsync(status, 0, 16 * sizeof(int), s));
-	FH_HIP(hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+	plan.upload(tab_dev, s);
 
-	// 1-3: T = Q^H lower(A) Q, diag / offdiag (mod.rs:326-356)
+	// 1-3: T = Q^H lower(A) Q, diag / offdiag (mod.rs:326-356); the strict upper triangle of A is never read
 	MatV<T> X{trid.as<T>(), n, n, 1, n};
-	typedef typename EvdBits<T>::U Bits;
+	typedef typename FloatBits<T>::U Bits;
 	Bits *amax = reinterpret_cast<Bits *>(status + 4); // {max |lower(A)|, max(|d|, |e|)}
 	T *fac = reinterpret_cast<T *>(status + 8);	    // their power-of-two factors
-	hipLaunchKernelGGL(evd_copy_lower_kernel<T>, dim3(blocks_for((idx_t) nn, 256)), dim3(256), 0, s, A.p, A.rs, A.cs, X.p, n, amax);
-	hipLaunchKernelGGL(evd_scale_kernel<T>, dim3(blocks_for((idx_t) nn, 256)), dim3(256), 0, s, X.p, (idx_t) nn, (const Bits *) amax, fac);
+	hipLaunchKernelGGL(dnc_copy_kernel<T>, dim3(blocks_for((idx_t) nn, 256)), dim3(256), 0, s, A.p, A.rs, A.cs, X.p, n, n, (int) DNC_LOWER, amax);
+	hipLaunchKernelGGL(dnc_scale_kernel<T>, dim3(blocks_for((idx_t) nn, 256)), dim3(256), 0, s, X.p, (idx_t) nn, (const Bits *) amax, fac);
 	MatV<T> H{hb.as<T>(), bs, n - 1, 1, bs};
 	if (n > 1)
 		tridiag_dev<T>(X, H);
-	hipLaunchKernelGGL(evd_extract_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, X.p, n, D, E, amax + 1, status);
-	hipLaunchKernelGGL(evd_tscale_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, D, E, n, (const Bits *) (amax + 1), fac + 1);
+	hipLaunchKernelGGL(dnc_extract_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const T *) X.p, n, (idx_t) 1, n, D, E, amax + 1, status);
+	hipLaunchKernelGGL(dnc_tscale_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, D, E, n, (const Bits *) (amax + 1), fac + 1);
 
 	// 4: tridiagonal divide and conquer (U buffer of depth d: d even -> u0, odd -> u1; the root writes u0)
 	MatV<T> u0 = want_u ? U : MatV<T>{ub0.as<T>(), n, n, 1, n};
 	MatV<T> u1{ub1.as<T>(), n, n, 1, n};
-	if (nmerges > 0)
-		hipLaunchKernelGGL(evd_tear_kernel<T>, dim3(blocks_for((idx_t) nmerges, 256)), dim3(256), 0, s, tab_dev + level_at[0],
-				   (int) nmerges, D, E, status);
-	{
-		static std::atomic<unsigned long long> attr_done{0}; // bit d: device d (the attribute is per device)
-		const int dev = ctx().device;
-		const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
-		const size_t lds = evd_leaf_lds<T>(EVD_LEAF_MAX);
-		if (bit == 0 || !(attr_done.load(std::memory_order_acquire) & bit)) {
-			FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&evd_leaf_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-			attr_done.fetch_or(bit, std::memory_order_release);
-		}
-		hipLaunchKernelGGL(evd_leaf_kernel<T>, dim3((unsigned) leaves.size()), dim3(64), evd_leaf_lds<T>((int) leaf), s, tab_dev, D, E, u0.p,
-				   u0.rs, u0.cs, u1.p, u1.rs, u1.cs, status);
-	}
+	if (plan.nmerges > 0)
+		hipLaunchKernelGGL(evd_tear_kernel<T>, dim3(blocks_for((idx_t) plan.nmerges, 256)), dim3(256), 0, s, tab_dev + plan.level_at[0],
+				   (int) plan.nmerges, D, E, status);
+	raise_dynamic_lds<&evd_leaf_kernel<T>>(evd_leaf_lds<T>(EVD_LEAF_MAX));
+	hipLaunchKernelGGL(evd_leaf_kernel<T>, dim3((unsigned) plan.leaves.size()), dim3(64), evd_leaf_lds<T>((int) leaf), s, tab_dev, D, E, u0.p, u0.rs,
+			   u0.cs, u1.p, u1.rs, u1.cs, status);
 	MatV<T> Q{qb.as<T>(), n, n, 1, n};
 	for (int lv = levels - 1; lv >= 0; --lv) {
-		const std::vector<EvdNode> &ms = merges[(size_t) lv];
-		const int *mt = tab_dev + level_at[(size_t) lv];
+		const std::vector<DncNode> &ms = plan.merges[(size_t) lv];
+		const int *mt = tab_dev + plan.level_at[(size_t) lv];
 		const unsigned cnt = (unsigned) ms.size();
-		idx_t maxn = 0;
-		for (const EvdNode &m : ms)
-			maxn = std::max(maxn, m.n);
+		const idx_t maxn = plan.maxn[(size_t) lv];
 		const MatV<T> src = (lv & 1) ? u0 : u1, dst = (lv & 1) ? u1 : u0; // children at depth lv + 1
 		hipLaunchKernelGGL(evd_merge_prep_kernel<T>, dim3(cnt), dim3(256), 0, s, mt, (const T *) D, (const T *) E, (const T *) src.p, src.rs,
 				   src.cs, w, status);
@@ -832,7 +648,7 @@ template <typename T> int self_adjoint_evd_dev(MatV<const T> A, MatV<T> U, T *S,
 		hipLaunchKernelGGL(evd_loewner_kernel<T>, dim3(blocks_for(maxn, 256), cnt), dim3(256), 0, s, mt, w, D, status);
 		hipLaunchKernelGGL(evd_qhat_kernel<T>, dim3((unsigned) maxn, cnt), dim3(256), 0, s, mt, w, Q.p, n, status);
 		FH_HIP(hipGetLastError());
-		for (const EvdNode &m : ms) {
+		for (const DncNode &m : ms) {
 			const idx_t o = m.off, n1 = m.n / 2, n2 = m.n - n1;
 			gemm_dev<T>(dst.sub(o, o, n1, m.n), DST_FULL, false, src.sub(o, o, n1, n1).c(), Q.sub(o, o, n1, m.n).c(), (T) 1);
 			gemm_dev<T>(dst.sub(o + n1, o, n2, m.n), DST_FULL, false, src.sub(o + n1, o + n1, n2, n2).c(), Q.sub(o + n1, o, n2, m.n).c(),
@@ -844,12 +660,9 @@ template <typename T> int self_adjoint_evd_dev(MatV<const T> A, MatV<T> U, T *S,
 	if (want_u && n > 1)
 		apply_householder_sequence_left_dev<T>(X.sub(1, 0, n - 1, n - 1).c(), H.c(), U.sub(1, 0, n - 1, n), false);
 	// 6: S
-	hipLaunchKernelGGL(evd_write_s_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const T *) D, n, S, ss, (const T *) fac);
+	hipLaunchKernelGGL(dnc_write_s_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const T *) D, n, S, ss, (const T *) fac);
 	FH_HIP(hipGetLastError());
-	int *st = ctx().pinned_ints();
-	FH_HIP(hipMemcpyAsync(st, status, sizeof(int), hipMemcpyDeviceToHost, s));
-	FH_HIP(hipStreamSynchronize(s)); // also keeps `tab` alive until its copy has run
-	return st[0];
+	return dnc_read_status(status, s); // its synchronization also keeps the plan alive until the copy of its table has run
 }
 
 template int self_adjoint_evd_dev<double>(MatV<const double>, MatV<double>, double *, idx_t, idx_t, idx_t);

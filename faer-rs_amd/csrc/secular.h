@@ -1,6 +1,6 @@
-// Scalar helpers, wavefront / workgroup reductions, Givens rotations and the secular equation root finder shared by the
-// divide and conquer solvers (evd.hip: symmetric tridiagonal, svd.hip: bidiagonal).  secular_root is the reference's
-// secular_eq_root_finder (svd/bidiag_svd.rs:7-270), which both of its solvers call.
+// Scalar helpers, wavefront / workgroup reductions, Givens rotations and the secular equation root finder of the divide
+// and conquer solvers (evd.hip: symmetric tridiagonal, svd.hip: bidiagonal; dnc.h has the driver scaffolding they share).
+// secular_root is the reference's secular_eq_root_finder (svd/bidiag_svd.rs:7-270), which both of its solvers call.
 #pragma once
 #include <cmath>
 
@@ -10,13 +10,13 @@ namespace fh {
 
 namespace {
 
-template <typename T> struct EvdTraits;
-template <> struct EvdTraits<double> {
+template <typename T> struct DncTraits;
+template <> struct DncTraits<double> {
 	static constexpr double eps = 2.220446049250313e-16;
 	static constexpr double sml = 2.2250738585072014e-308;
 	static constexpr long iter_factor = 32; // max(30, nbits / 2)
 };
-template <> struct EvdTraits<float> {
+template <> struct DncTraits<float> {
 	static constexpr float eps = 1.1920929e-07f;
 	static constexpr float sml = 1.17549435e-38f;
 	static constexpr long iter_factor = 30;
@@ -102,7 +102,7 @@ template <typename T> struct SecularEq {
 
 template <typename T, typename F> __device__ void secular_root(const F &f, T left, T right, bool last, T &shift_out, T &mu_out)
 {
-	const T two = 2, eight = 8, one_half = 0.5, epsilon = EvdTraits<T>::eps;
+	const T two = 2, eight = 8, one_half = 0.5, epsilon = DncTraits<T>::eps;
 	// loop caps: none is reached by a convergent search, they only keep a non-finite input from spinning
 	constexpr int SECANT_CAP = 256, BISECT_CAP = 2200;
 	const T mid = left + (right - left) * one_half;

@@ -36,27 +36,13 @@
 #include <cmath>
 
 #include "common.h"
-#include "secular.h"
+#include "dnc.h"
 
 namespace fh {
 
 namespace {
 
 constexpr int SVD_LEAF_MAX = 64;
-
-template <typename T> struct SvdBits;
-template <> struct SvdBits<double> {
-	typedef unsigned long long U;
-	static __device__ U of(double x) { return (U) __double_as_longlong(x); }
-	static __device__ double val(U u) { return __longlong_as_double((long long) u); }
-	static constexpr double rmin = 1.0010415475915505e-146, rmax = 9.989595361011175e+145; // sqrt(sml / eps), 1 / rmin
-};
-template <> struct SvdBits<float> {
-	typedef unsigned int U;
-	static __device__ U of(float x) { return __float_as_uint(x); }
-	static __device__ float val(U u) { return __uint_as_float(u); }
-	static constexpr float rmin = 3.1401849e-16f, rmax = 3.1845258e+15f;
-};
 
 // per-level work vectors (a merge at offset `off` owns [off, off + n)); per-merge scalars by the merge's index in its level
 template <typename T> struct SvdWork {
@@ -69,87 +55,6 @@ template <typename T> struct SvdWork {
 	T *sc;	  // 4 per merge: c0, s0, max, |col0|
 	int *cnt; // 8 per merge: zero node, m (non-deflated), actual_n by col0, n0i, nij
 };
-
-// ---- input --------------------------------------------------------------------------------------
-// X <- A (dense column major) and max |A| (the bits of a non-negative float order like unsigned integers)
-template <typename T>
-__global__ __launch_bounds__(256) void svd_copy_kernel(const T *A, idx_t rs, idx_t cs, T *X, idx_t m, idx_t n, bool upper,
-							typename SvdBits<T>::U *amax)
-{
-	__shared__ T red[4];
-	const idx_t t = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	T v = 0;
-	if (t < m * n) {
-		const idx_t i = t % m, j = t / m;
-		v = (!upper || i <= j) ? A[i * rs + j * cs] : (T) 0;
-		X[t] = v;
-	}
-	const T mx = block_reduce<T, true>(ev_abs(v), red);
-	if (threadIdx.x == 0)
-		atomicMax(amax, SvdBits<T>::of(mx));
-}
-
-// a matrix whose largest entry lies outside [rmin, rmax] is scaled by a power of two into that range (exact), the singular
-// values are scaled back at the end; fac[0] <- the factor (1 inside the range)
-template <typename T> __global__ void svd_scale_kernel(T *X, idx_t nn, const typename SvdBits<T>::U *amax, T *fac)
-{
-	const T a = SvdBits<T>::val(*amax);
-	int e = 0;
-	if (isfinite(a) && a > (T) 0) {
-		if (a > SvdBits<T>::rmax)
-			e = ilogb((double) SvdBits<T>::rmax) - ilogb((double) a) - 1;
-		else if (a < SvdBits<T>::rmin)
-			e = ilogb((double) SvdBits<T>::rmin) - ilogb((double) a) + 1;
-	}
-	if (e == 0) {
-		if (blockIdx.x == 0 && threadIdx.x == 0)
-			fac[0] = 1;
-		return;
-	}
-	const T f = (T) ldexp(1.0, e);
-	const idx_t t = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if (t < nn)
-		X[t] *= f;
-	if (t == 0)
-		fac[0] = f;
-}
-
-// diag / superdiag of the bidiagonal form (mod.rs:385-392) and their largest magnitude; a non-finite entry sets the status
-// (:282-286)
-template <typename T>
-__global__ __launch_bounds__(256) void svd_extract_kernel(const T *X, idx_t ldx, idx_t n, T *D, T *E, typename SvdBits<T>::U *tmax, int *status)
-{
-	__shared__ T red[4];
-	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	T m = 0;
-	if (i < n) {
-		const T d = X[i + i * ldx];
-		const T e = i + 1 < n ? X[i + (i + 1) * ldx] : (T) 0;
-		D[i] = d;
-		E[i] = e;
-		if (!isfinite(d) || !isfinite(e))
-			status[0] = 1;
-		m = ev_max(ev_abs(d), ev_abs(e));
-	}
-	m = block_reduce<T, true>(m, red);
-	if (threadIdx.x == 0)
-		atomicMax(tmax, SvdBits<T>::of(m));
-}
-
-// the bidiagonal scaled by a power of two (exact) to max(|d|, |e|) in [1, 2); tfac[0] <- the factor
-template <typename T> __global__ void svd_tscale_kernel(T *D, T *E, idx_t n, const typename SvdBits<T>::U *tmax, T *tfac)
-{
-	const T a = SvdBits<T>::val(*tmax);
-	const int e = isfinite(a) && a > (T) 0 ? -ilogb((double) a) : 0;
-	const T f = (T) ldexp(1.0, e);
-	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) {
-		D[i] *= f;
-		E[i] *= f;
-	}
-	if (i == 0)
-		tfac[0] = f;
-}
 
 // ---- leaves -------------------------------------------------------------------------------------
 constexpr int svd_leaf_ld(int m) { return (m + 1) | 1; }
@@ -178,7 +83,7 @@ __global__ __launch_bounds__(64) void svd_leaf_kernel(const int *leaves, const T
 	T *d = q + (size_t) m * ld, *e = d + (SVD_LEAF_MAX + 1);
 	T *c1 = e + (SVD_LEAF_MAX + 1), *s1 = c1 + (SVD_LEAF_MAX + 1), *c2 = s1 + (SVD_LEAF_MAX + 1), *s2 = c2 + (SVD_LEAF_MAX + 1);
 	int *perm = reinterpret_cast<int *>(s2 + (SVD_LEAF_MAX + 1));
-	const T eps = EvdTraits<T>::eps, sml = EvdTraits<T>::sml;
+	const T eps = DncTraits<T>::eps, sml = DncTraits<T>::sml;
 
 	for (int t = tid; t < (m + 1) * ld; t += 64)
 		p[t] = (t % ld) == (t / ld) ? (T) 1 : (T) 0;
@@ -232,7 +137,7 @@ __global__ __launch_bounds__(64) void svd_leaf_kernel(const int *leaves, const T
 			e[i] *= inv;
 		}
 		__syncthreads();
-		const long max_iters = EvdTraits<T>::iter_factor * (long) m * (long) m;
+		const long max_iters = DncTraits<T>::iter_factor * (long) m * (long) m;
 		const T eps2 = eps * eps;
 		for (long iter = 0; iter < max_iters; ++iter) {
 			for (int i = tid; i + 1 < m; i += 64)
@@ -277,7 +182,6 @@ __global__ __launch_bounds__(64) void svd_leaf_kernel(const int *leaves, const T
 				__syncthreads();
 				if (want_q)
 					for (int r = tid; r < m; r += 64) {
-						// rot.adjoint().apply_on_the_right_in_place on columns (j, i)
 						T *row = q + (size_t) r * ld;
 						T y = row[i];
 						for (int j = i + 1; j < end; ++j) {
@@ -344,28 +248,11 @@ __global__ __launch_bounds__(64) void svd_leaf_kernel(const int *leaves, const T
 				}
 			}
 			__syncthreads();
-			// apply_on_the_right_in_place on columns (k + 1, k): X(:, k+1) = c a + s b, X(:, k) = c b - s a
-			for (int r = tid; r <= m; r += 64) {
-				T *row = p + (size_t) r * ld;
-				T x = row[start];
-				for (int k = start; k < end - 1; ++k) {
-					const T a = row[k + 1], c = c1[k], s = s1[k];
-					row[k] = c * x - s * a;
-					x = c * a + s * x;
-				}
-				row[end - 1] = x;
-			}
+			for (int r = tid; r <= m; r += 64)
+				rot_chain_forward(p + (size_t) r * ld, start, end - 1, c1, s1);
 			if (want_q)
-				for (int r = tid; r < m; r += 64) {
-					T *row = q + (size_t) r * ld;
-					T x = row[start];
-					for (int k = start; k < end - 1; ++k) {
-						const T a = row[k + 1], c = c2[k], s = s2[k];
-						row[k] = c * x - s * a;
-						x = c * a + s * x;
-					}
-					row[end - 1] = x;
-				}
+				for (int r = tid; r < m; r += 64)
+					rot_chain_forward(q + (size_t) r * ld, start, end - 1, c2, s2);
 			__syncthreads();
 			if (iter + 1 == max_iters) {
 				fail = true;
@@ -439,7 +326,7 @@ __global__ __launch_bounds__(256) void svd_merge_prep_kernel(const int *merges, 
 	const int b = blockIdx.x, tid = threadIdx.x;
 	const idx_t off = merges[3 * b];
 	const int n = merges[3 * b + 1], k = merges[3 * b + 2];
-	const T eps = EvdTraits<T>::eps, sml = EvdTraits<T>::sml;
+	const T eps = DncTraits<T>::eps, sml = DncTraits<T>::sml;
 	T *dt = w.dt + off, *ct = w.ct + off, *dg = w.dg + off, *c0 = w.c0 + off, *dp = w.dp + off, *zp = w.zp + off;
 	T *jc = w.jc + off, *js = w.js + off;
 	int *op = w.op + off, *pm = w.pm + off, *nxt = w.nxt + off, *jidx = w.jidx + off, *ord = w.tmp + off;
@@ -682,7 +569,7 @@ template <typename T> __global__ __launch_bounds__(256) void svd_secular_kernel(
 	// 9 N eps ||A|| in fp32, where such entries are common).  f increases with mu on (0, right - left) for the left pole and on
 	// (left - right, 0) for the right one: a root that does not separate the signs of f at mu (1 -+ 16 eps) is bisected.
 	{
-		const T eps = EvdTraits<T>::eps, tol = (T) 16 * eps;
+		const T eps = DncTraits<T>::eps, tol = (T) 16 * eps;
 		const T a = mu * ((T) 1 - tol), b = mu * ((T) 1 + tol);
 		const T lo = a < b ? a : b, hi = a < b ? b : a;
 		const T flo = f(shift, lo), fhi = f(shift, hi);
@@ -897,13 +784,6 @@ __global__ __launch_bounds__(256) void svd_vectors_kernel(const int *merges, Svd
 }
 
 // ---- output -------------------------------------------------------------------------------------
-template <typename T> __global__ void svd_write_s_kernel(const T *D, idx_t n, T *S, idx_t ss, const T *fac) // fac: {A scale, B scale}
-{
-	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n)
-		S[i * ss] = D[i] * ((T) 1 / fac[0]) * ((T) 1 / fac[1]);
-}
-
 // dst (m x nc) <- src (n x n, column major) in its top left corner, zero elsewhere, ones on the rest of the diagonal
 // (mod.rs:405-411)
 template <typename T> __global__ void svd_place_kernel(T *dst, idx_t rs, idx_t cs, idx_t m, idx_t nc, const T *src, idx_t lds, idx_t n)
@@ -915,61 +795,19 @@ template <typename T> __global__ void svd_place_kernel(T *dst, idx_t rs, idx_t c
 	dst[i * rs + j * cs] = i < n && j < n ? src[i + j * lds] : (i == j ? (T) 1 : (T) 0);
 }
 
-struct SvdNode {
-	idx_t off, n;
-	int depth;
-};
-
-void svd_plan(idx_t off, idx_t n, int depth, idx_t leaf, std::vector<SvdNode> &leaves, std::vector<std::vector<SvdNode>> &merges)
-{
-	if (n <= leaf) {
-		leaves.push_back(SvdNode{off, n, depth});
-		return;
-	}
-	if ((int) merges.size() <= depth)
-		merges.resize((size_t) depth + 1);
-	merges[(size_t) depth].push_back(SvdNode{off, n, depth});
-	const idx_t k = n / 2;
-	svd_plan(off, k, depth + 1, leaf, leaves, merges);
-	svd_plan(off + k + 1, n - k - 1, depth + 1, leaf, leaves, merges);
-}
-
-inline unsigned svd_blocks(idx_t count, int per) { return (unsigned) ((count + per - 1) / per); }
-
 // The SVD of a tall or square device matrix M (m >= n >= 1) through its bidiagonal form (mod.rs:326-431, svd_imp).
 // Uo: m x nu (nu = n or m) or .p == nullptr, Vo: n x n or .p == nullptr; S with stride ss.  Launches only; `status` is read by
 // the caller.  `upper`: only the upper triangle of M is read (the R factor of the QR pre-step).
 template <typename T>
-void svd_squareish(MatV<const T> M, bool upper, MatV<T> Uo, MatV<T> Vo, T *S, idx_t ss, idx_t leaf, idx_t bs, int *status,
-		   std::vector<int> &tab)
+void svd_squareish(MatV<const T> M, bool upper, MatV<T> Uo, MatV<T> Vo, T *S, idx_t ss, idx_t leaf, idx_t bs, int *status)
 {
 	const idx_t m = M.nrows, n = M.ncols;
 	hipStream_t s = ctx().stream;
 	const bool want_u = Uo.p != nullptr, want_v = Vo.p != nullptr;
 	const int want_q = want_u ? 1 : 0;
 
-	std::vector<SvdNode> leaves;
-	std::vector<std::vector<SvdNode>> merges;
-	svd_plan(0, n, 0, leaf, leaves, merges);
-	const int levels = (int) merges.size();
-	tab.clear();
-	for (const SvdNode &l : leaves) {
-		tab.push_back((int) l.off);
-		tab.push_back((int) l.n);
-		tab.push_back(l.depth & 1);
-	}
-	std::vector<size_t> level_at((size_t) levels);
-	size_t max_level = 0;
-	for (int lv = 0; lv < levels; ++lv) {
-		level_at[(size_t) lv] = tab.size();
-		max_level = std::max(max_level, merges[(size_t) lv].size());
-		for (const SvdNode &mg : merges[(size_t) lv]) {
-			tab.push_back((int) mg.off);
-			tab.push_back((int) mg.n);
-			tab.push_back((int) (mg.n / 2));
-		}
-	}
-	FH_CHECK(leaves.size() < (1u << 31) && max_level < 65536, "svd: too many nodes");
+	const DncPlan plan(n, leaf, 1, "svd: too many nodes");
+	const int levels = plan.levels();
 
 	const idx_t n1 = n + 1;
 	const size_t pp = (size_t) n1 * (size_t) n1, qq = (size_t) n * (size_t) n;
@@ -977,75 +815,57 @@ void svd_squareish(MatV<const T> M, bool upper, MatV<T> Uo, MatV<T> Vo, T *S, id
 	Scratch pb0(pp * sizeof(T)), pb1(levels > 0 ? pp * sizeof(T) : 16), wb(levels > 0 ? pp * sizeof(T) : 16), tpb(levels > 0 ? pp * sizeof(T) : 16);
 	Scratch qb0(want_q ? qq * sizeof(T) : 16), qb1(want_q && levels > 0 ? qq * sizeof(T) : 16), wqb(want_q && levels > 0 ? qq * sizeof(T) : 16),
 		tqb(want_q && levels > 0 ? qq * sizeof(T) : 16);
-	Scratch vec((size_t) 19 * (size_t) n1 * sizeof(T) + (size_t) 14 * (size_t) n1 * sizeof(int) + 64), tb(tab.size() * sizeof(int) + 16);
+	Scratch vec((size_t) 19 * (size_t) n1 * sizeof(T) + (size_t) 14 * (size_t) n1 * sizeof(int) + 64), tb(plan.tab_bytes() + 16);
 	T *D0 = vec.as<T>(), *E0 = D0 + n1, *D = E0 + n1;
 	SvdWork<T> w;
 	{
 		T *p = D + n1;
-		T **tp[] = {&w.dt, &w.ct, &w.dg, &w.c0, &w.dp, &w.zp, &w.sh, &w.mu, &w.sv, &w.zh, &w.jc, &w.js};
-		for (T **q : tp) {
-			*q = p;
-			p += n1;
-		}
+		dnc_carve(p, n1, {&w.dt, &w.ct, &w.dg, &w.c0, &w.dp, &w.zp, &w.sh, &w.mu, &w.sv, &w.zh, &w.jc, &w.js});
 		w.sc = p;
 		p += 4 * n1;
 		int *ip = reinterpret_cast<int *>(p);
-		int **ipp[] = {&w.op, &w.pm, &w.nxt, &w.jidx, &w.colpos, &w.tmp};
-		for (int **q : ipp) {
-			*q = ip;
-			ip += n1;
-		}
+		dnc_carve(ip, n1, {&w.op, &w.pm, &w.nxt, &w.jidx, &w.colpos, &w.tmp});
 		w.cnt = ip;
 	}
 	int *tab_dev = tb.as<int>();
-	FH_HIP(hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+	plan.upload(tab_dev, s);
 
 	// B = Ul^H M Ur, diag / superdiag (mod.rs:347-392)
 	MatV<T> X{xb.as<T>(), m, n, 1, m};
-	typedef typename SvdBits<T>::U Bits;
+	typedef typename FloatBits<T>::U Bits;
 	Bits *amax = reinterpret_cast<Bits *>(status + 4); // {max |M|, max(|d|, |e|)}
 	T *fac = reinterpret_cast<T *>(status + 8);	    // their power-of-two factors
 	FH_HIP(hipMemsetAsync(status + 4, 0, 12 * sizeof(int), s));
 	const idx_t mn = m * n;
-	hipLaunchKernelGGL(svd_copy_kernel<T>, dim3(svd_blocks(mn, 256)), dim3(256), 0, s, M.p, M.rs, M.cs, X.p, m, n, upper, amax);
-	hipLaunchKernelGGL(svd_scale_kernel<T>, dim3(svd_blocks(mn, 256)), dim3(256), 0, s, X.p, mn, (const Bits *) amax, fac);
+	hipLaunchKernelGGL(dnc_copy_kernel<T>, dim3(blocks_for(mn, 256)), dim3(256), 0, s, M.p, M.rs, M.cs, X.p, m, n, (int) (upper ? DNC_UPPER : DNC_ALL),
+			   amax);
+	hipLaunchKernelGGL(dnc_scale_kernel<T>, dim3(blocks_for(mn, 256)), dim3(256), 0, s, X.p, mn, (const Bits *) amax, fac);
 	MatV<T> Hl{hlb.as<T>(), bs, n, 1, bs}, Hr{hrb.as<T>(), bs, n - 1, 1, bs};
 	bidiag_dev<T>(X, Hl, Hr);
-	hipLaunchKernelGGL(svd_extract_kernel<T>, dim3(svd_blocks(n, 256)), dim3(256), 0, s, (const T *) X.p, m, n, D0, E0, amax + 1, status);
-	hipLaunchKernelGGL(svd_tscale_kernel<T>, dim3(svd_blocks(n, 256)), dim3(256), 0, s, D0, E0, n, (const Bits *) (amax + 1), fac + 1);
+	hipLaunchKernelGGL(dnc_extract_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const T *) X.p, m, m, n, D0, E0, amax + 1, status);
+	hipLaunchKernelGGL(dnc_tscale_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, D0, E0, n, (const Bits *) (amax + 1), fac + 1);
 
 	// bidiagonal divide and conquer (factors of depth d: d even -> buffer 0, odd -> buffer 1; the root writes buffer 0)
 	MatV<T> p0{pb0.as<T>(), n1, n1, 1, n1}, p1{pb1.as<T>(), n1, n1, 1, n1}, W{wb.as<T>(), n1, n1, 1, n1};
 	MatV<T> q0{qb0.as<T>(), n, n, 1, n}, q1{qb1.as<T>(), n, n, 1, n}, Wq{wqb.as<T>(), n, n, 1, n};
-	{
-		static std::atomic<unsigned long long> attr_done{0}; // bit d: device d (the attribute is per device)
-		const int dev = ctx().device;
-		const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
-		const size_t lds = svd_leaf_lds<T>(SVD_LEAF_MAX);
-		if (bit == 0 || !(attr_done.load(std::memory_order_acquire) & bit)) {
-			FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&svd_leaf_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-			attr_done.fetch_or(bit, std::memory_order_release);
-		}
-		hipLaunchKernelGGL(svd_leaf_kernel<T>, dim3((unsigned) leaves.size()), dim3(64), svd_leaf_lds<T>((int) leaf), s, (const int *) tab_dev,
-				   (const T *) D0, (const T *) E0, D, p0.p, p1.p, n1, q0.p, q1.p, n, want_q, status);
-	}
+	raise_dynamic_lds<&svd_leaf_kernel<T>>(svd_leaf_lds<T>(SVD_LEAF_MAX));
+	hipLaunchKernelGGL(svd_leaf_kernel<T>, dim3((unsigned) plan.leaves.size()), dim3(64), svd_leaf_lds<T>((int) leaf), s, (const int *) tab_dev,
+			   (const T *) D0, (const T *) E0, D, p0.p, p1.p, n1, q0.p, q1.p, n, want_q, status);
 	for (int lv = levels - 1; lv >= 0; --lv) {
-		const std::vector<SvdNode> &ms = merges[(size_t) lv];
-		const int *mt = tab_dev + level_at[(size_t) lv];
+		const std::vector<DncNode> &ms = plan.merges[(size_t) lv];
+		const int *mt = tab_dev + plan.level_at[(size_t) lv];
 		const unsigned cnt = (unsigned) ms.size();
-		idx_t maxn = 0;
-		for (const SvdNode &mg : ms)
-			maxn = std::max(maxn, mg.n);
+		const idx_t maxn = plan.maxn[(size_t) lv];
 		const MatV<T> ps = (lv & 1) ? p0 : p1, pd = (lv & 1) ? p1 : p0; // children at depth lv + 1
 		const MatV<T> qs = (lv & 1) ? q0 : q1, qd = (lv & 1) ? q1 : q0;
 		hipLaunchKernelGGL(svd_merge_prep_kernel<T>, dim3(cnt), dim3(256), 0, s, mt, (const T *) D0, (const T *) E0, (const T *) D,
 				   (const T *) ps.p, n1, w, (const int *) status);
-		hipLaunchKernelGGL(svd_secular_kernel<T>, dim3(svd_blocks(maxn, 4), cnt), dim3(256), 0, s, mt, w, (const int *) status);
-		hipLaunchKernelGGL(svd_zhat_kernel<T>, dim3(svd_blocks(maxn, 256), cnt), dim3(256), 0, s, mt, w, D, (const int *) status);
+		hipLaunchKernelGGL(svd_secular_kernel<T>, dim3(blocks_for(maxn, 4), cnt), dim3(256), 0, s, mt, w, (const int *) status);
+		hipLaunchKernelGGL(svd_zhat_kernel<T>, dim3(blocks_for(maxn, 256), cnt), dim3(256), 0, s, mt, w, D, (const int *) status);
 		hipLaunchKernelGGL(svd_vectors_kernel<T>, dim3((unsigned) maxn, cnt), dim3(256), 0, s, mt, w, W.p, tpb.as<T>(), n1, Wq.p, tqb.as<T>(), n,
 				   want_q, (const int *) status);
 		FH_HIP(hipGetLastError());
-		for (const SvdNode &mg : ms) {
+		for (const DncNode &mg : ms) {
 			const idx_t o = mg.off, nn = mg.n, k = nn / 2, rem = nn - k - 1;
 			gemm_dev<T>(pd.sub(o, o, k + 1, nn + 1), DST_FULL, false, ps.sub(o, o, k + 1, k + 1).c(), W.sub(o, o, k + 1, nn + 1).c(), (T) 1);
 			gemm_dev<T>(pd.sub(o + k + 1, o, rem + 1, nn + 1), DST_FULL, false, ps.sub(o + k + 1, o + k + 1, rem + 1, rem + 1).c(),
@@ -1061,34 +881,30 @@ void svd_squareish(MatV<const T> M, bool upper, MatV<T> Uo, MatV<T> Vo, T *S, id
 
 	// U = Ul [Q 0; 0 I], V = Ur [1 0; 0 .] P[0:n, 0:n] (mod.rs:403-429)
 	if (want_u) {
-		hipLaunchKernelGGL(svd_place_kernel<T>, dim3(svd_blocks(m * Uo.ncols, 256)), dim3(256), 0, s, Uo.p, Uo.rs, Uo.cs, m, Uo.ncols,
+		hipLaunchKernelGGL(svd_place_kernel<T>, dim3(blocks_for(m * Uo.ncols, 256)), dim3(256), 0, s, Uo.p, Uo.rs, Uo.cs, m, Uo.ncols,
 				   (const T *) q0.p, n, n);
 		apply_householder_sequence_left_dev<T>(X.c(), Hl.c(), Uo, false);
 	}
 	if (want_v) {
-		hipLaunchKernelGGL(svd_place_kernel<T>, dim3(svd_blocks(n * n, 256)), dim3(256), 0, s, Vo.p, Vo.rs, Vo.cs, n, n, (const T *) p0.p, n1, n);
+		hipLaunchKernelGGL(svd_place_kernel<T>, dim3(blocks_for(n * n, 256)), dim3(256), 0, s, Vo.p, Vo.rs, Vo.cs, n, n, (const T *) p0.p, n1, n);
 		if (n > 1)
 			apply_householder_sequence_left_dev<T>(X.sub(0, 1, n - 1, n - 1).t().c(), Hr.c(), Vo.sub(1, 0, n - 1, n), false);
 	}
-	hipLaunchKernelGGL(svd_write_s_kernel<T>, dim3(svd_blocks(n, 256)), dim3(256), 0, s, (const T *) D, n, S, ss, (const T *) fac);
+	hipLaunchKernelGGL(dnc_write_s_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const T *) D, n, S, ss, (const T *) fac);
 	FH_HIP(hipGetLastError());
-	FH_HIP(hipStreamSynchronize(s)); // `tab` and the scratch of this frame stay alive until their work has run
+	FH_HIP(hipStreamSynchronize(s)); // the plan and the scratch of this frame stay alive until their work has run
 }
 
 } // namespace
 
 // Leaves of min(max(recursion_threshold, 4), 64) entries for both dtypes (the header comment has the LDS budget).
-idx_t svd_leaf_size(size_t recursion_threshold)
-{
-	const size_t t = recursion_threshold < 4 ? 4 : recursion_threshold;
-	return (idx_t) (t > (size_t) SVD_LEAF_MAX ? (size_t) SVD_LEAF_MAX : t);
-}
+idx_t svd_leaf_size(size_t recursion_threshold) { return dnc_leaf_size(recursion_threshold, SVD_LEAF_MAX); }
 
 template <typename T> void svd_identity_dev(MatV<T> X)
 {
 	if (X.nrows == 0 || X.ncols == 0)
 		return;
-	hipLaunchKernelGGL(svd_place_kernel<T>, dim3(svd_blocks(X.nrows * X.ncols, 256)), dim3(256), 0, ctx().stream, X.p, X.rs, X.cs, X.nrows,
+	hipLaunchKernelGGL(svd_place_kernel<T>, dim3(blocks_for(X.nrows * X.ncols, 256)), dim3(256), 0, ctx().stream, X.p, X.rs, X.cs, X.nrows,
 			   X.ncols, (const T *) nullptr, (idx_t) 0, (idx_t) 0);
 	FH_HIP(hipGetLastError());
 }
@@ -1111,9 +927,8 @@ int svd_dev(MatV<const T> A, MatV<T> U, MatV<T> V, T *S, idx_t ss, idx_t leaf, d
 	Scratch stb(16 * sizeof(int));
 	int *status = stb.as<int>();
 	FH_HIP(hipMemsetAsync(status, 0, 16 * sizeof(int), s));
-	std::vector<int> tab;
 	if ((double) m / (double) n <= qr_ratio_threshold) {
-		svd_squareish<T>(A, false, U, V, S, ss, leaf, bs_mn, status, tab);
+		svd_squareish<T>(A, false, U, V, S, ss, leaf, bs_mn, status);
 	} else {
 		// mod.rs:604-661: A = Q R, the SVD of R, U <- Q [U_R; 0 (I)]
 		Scratch xb((size_t) m * (size_t) n * sizeof(T)), hb((size_t) bs_mn * (size_t) n * sizeof(T));
@@ -1123,18 +938,15 @@ int svd_dev(MatV<const T> A, MatV<T> U, MatV<T> V, T *S, idx_t ss, idx_t leaf, d
 		const bool want_u = U.p != nullptr;
 		Scratch ub(want_u ? (size_t) n * (size_t) n * sizeof(T) : 16);
 		const MatV<T> Ur{want_u ? ub.as<T>() : nullptr, n, n, 1, n};
-		svd_squareish<T>(X.sub(0, 0, n, n).c(), true, Ur, V, S, ss, leaf, bs_nn, status, tab);
+		svd_squareish<T>(X.sub(0, 0, n, n).c(), true, Ur, V, S, ss, leaf, bs_nn, status);
 		if (want_u) {
-			hipLaunchKernelGGL(svd_place_kernel<T>, dim3(svd_blocks(m * U.ncols, 256)), dim3(256), 0, s, U.p, U.rs, U.cs, m, U.ncols,
+			hipLaunchKernelGGL(svd_place_kernel<T>, dim3(blocks_for(m * U.ncols, 256)), dim3(256), 0, s, U.p, U.rs, U.cs, m, U.ncols,
 					   (const T *) Ur.p, n, n);
 			FH_HIP(hipGetLastError());
 			apply_householder_sequence_left_dev<T>(X.c(), H.c(), U, false);
 		}
 	}
-	int *st = ctx().pinned_ints();
-	FH_HIP(hipMemcpyAsync(st, status, sizeof(int), hipMemcpyDeviceToHost, s));
-	FH_HIP(hipStreamSynchronize(s));
-	return st[0];
+	return dnc_read_status(status, s);
 }
 
 template int svd_dev<double>(MatV<const double>, MatV<double>, MatV<double>, double *, idx_t, idx_t, double, idx_t, idx_t, idx_t);

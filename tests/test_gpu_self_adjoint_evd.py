@@ -171,6 +171,20 @@ def test_recursion_threshold_values(dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rt", [4, 64])
+@pytest.mark.parametrize("with_u", [True, False])
+def test_deterministic(dtype, rt, with_u):
+    """n = 130: with 64-row leaves the smallest size that has two merge levels with unequal halves"""
+    F = init_gpu()
+    a = sym(np.random.default_rng(130), 130, dtype)
+    (tag1, s1, u1), (tag2, s2, u2) = (run(F, a, with_u=with_u, prm=params(F, dtype, rt)) for _ in range(2))
+    assert tag1 == tag2 == F.EVD_OK
+    assert np.array_equal(s1, s2)
+    if with_u:
+        assert np.array_equal(u1, u2)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_host_operands(dtype):
     F = init_gpu()
     n = 200
