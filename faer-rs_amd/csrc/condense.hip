@@ -73,6 +73,43 @@ template <typename T> static __device__ __forceinline__ T lv2_householder(T &hea
 	return (T) 0.5 * ((T) 1 + tn * tn);
 }
 
+// one entry more in the three scaled sums of squares of a norm (reductions/norm_l2.rs:6-45).  A macro: as an inline function the same three
+// statements make the compiler pack the fp32 products of the vector kernels differently
+#define LV2_NORM_ACC(acc, v, sml, big) \
+	do { \
+		(acc)[0] += ((v) * (sml)) * ((v) * (sml)); \
+		(acc)[1] += (v) * (v); \
+		(acc)[2] += ((v) * (big)) * ((v) * (big)); \
+	} while (0)
+
+// the sum of the `np` shares src[p * stride] in the order of p, eight loads in flight
+static __device__ __forceinline__ double lv2_sum_shares(const double *src, const int np, const size_t stride)
+{
+	double s0 = 0.0;
+	int p = 0;
+	for (; p + 8 <= np; p += 8) {
+		double v[8];
+#pragma unroll
+		for (int u = 0; u < 8; ++u)
+			v[u] = src[(size_t) (p + u) * stride];
+#pragma unroll
+		for (int u = 0; u < 8; ++u)
+			s0 += v[u];
+	}
+	for (; p < np; ++p)
+		s0 += src[(size_t) p * stride];
+	return s0;
+}
+
+// end of a helper block of a vector kernel: its write-through stores have left, then ONE flag tells block 0 of the same launch (xwg.h)
+static __device__ __forceinline__ void lv2_helper_done(xwg_u64 *flag, const xwg_u64 epoch)
+{
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	__syncthreads();
+	if (threadIdx.x == 0)
+		__hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Tridiagonalization of a self-adjoint matrix -- faer/src/linalg/evd/tridiag.rs:274-535.
 // A level-2, HBM-bound algorithm like the reference's: per column ONE pass over the remaining lower triangle that
@@ -202,9 +239,7 @@ template <typename T> static __device__ __forceinline__ void td_step_body(const 
 			const T v = at(i, k) - (y1 * xi + yi);
 			at(i, k) = v;
 			if (i >= k + 2) {
-				nacc[0] += (v * sml) * (v * sml);
-				nacc[1] += v * v;
-				nacc[2] += (v * big) * (v * big);
+				LV2_NORM_ACC(nacc, v, sml, big);
 			}
 		}
 		if (tid == 0) {
@@ -214,9 +249,7 @@ template <typename T> static __device__ __forceinline__ void td_step_body(const 
 	} else {
 		for (int i = 2 + tid; i < n; i += LV2_NT) {
 			const T v = at(i, 0);
-			nacc[0] += (v * sml) * (v * sml);
-			nacc[1] += v * v;
-			nacc[2] += (v * big) * (v * big);
+			LV2_NORM_ACC(nacc, v, sml, big);
 		}
 	}
 	if (k + 1 >= n)
@@ -225,26 +258,10 @@ template <typename T> static __device__ __forceinline__ void td_step_body(const 
 	double accd[3] = {(double) nacc[0], (double) nacc[1], (double) nacc[2]};
 	block_sum<LV2_NT, 3>(accd, s_part, s_red); // (its barriers also publish the column written above)
 	const T tail_norm = norm_from3<T>(s_red);
-	T head = at(k + 1, k);
-	T head_norm = fabs(head);
-	if (head_norm < Lim<T>::minpos) {
-		head = (T) 0;
-		head_norm = (T) 0;
-	}
-	T tau, hinv = (T) 0;
-	bool scale_tail = false;
-	if (tail_norm < Lim<T>::minpos) {
-		tau = std::numeric_limits<T>::infinity();
-	} else {
-		const T norm = (T) hypot((double) head_norm, (double) tail_norm);
-		const T sign = head_norm != (T) 0 ? head * ((T) 1 / head_norm) : (T) 1;
-		const T signed_norm = sign * norm;
-		hinv = (T) 1 / (head + signed_norm);
-		head = -signed_norm;
-		const T tn = tail_norm * fabs(hinv);
-		tau = (T) 0.5 * ((T) 1 + tn * tn);
-		scale_tail = true;
-	}
+	T head = at(k + 1, k), hinv;
+	bool negligible;
+	const T tau = lv2_householder<T>(head, tail_norm, hinv, negligible);
+	const bool scale_tail = !negligible;
 	__syncthreads(); // everyone has read the old head
 	const T u1 = k > 0 ? at(k + 1, k - 1) : (T) 0, y1n = k > 0 ? a.y[k + 1] : (T) 0;
 	for (int i = k + 2 + tid; i < n; i += LV2_NT) {
@@ -332,9 +349,7 @@ template <typename T> static __device__ __forceinline__ void td_step_body_reg(co
 		const int i = k + 1 + tid + e * LV2_NT;
 		if (i < n && i >= k + 2) {
 			const T v = aik[e];
-			nacc[0] += (v * sml) * (v * sml);
-			nacc[1] += v * v;
-			nacc[2] += (v * big) * (v * big);
+			LV2_NORM_ACC(nacc, v, sml, big);
 		}
 	}
 	if (tid == 0 && upd)
@@ -350,26 +365,10 @@ template <typename T> static __device__ __forceinline__ void td_step_body_reg(co
 	double accd[3] = {(double) nacc[0], (double) nacc[1], (double) nacc[2]};
 	block_sum<LV2_NT, 3>(accd, s_part, s_red);
 	const T tail_norm = norm_from3<T>(s_red);
-	T head = s_bc[0];
-	T head_norm = fabs(head);
-	if (head_norm < Lim<T>::minpos) {
-		head = (T) 0;
-		head_norm = (T) 0;
-	}
-	T tau, hinv = (T) 0;
-	bool scale_tail = false;
-	if (tail_norm < Lim<T>::minpos) {
-		tau = std::numeric_limits<T>::infinity();
-	} else {
-		const T norm = (T) hypot((double) head_norm, (double) tail_norm);
-		const T sign = head_norm != (T) 0 ? head * ((T) 1 / head_norm) : (T) 1;
-		const T signed_norm = sign * norm;
-		hinv = (T) 1 / (head + signed_norm);
-		head = -signed_norm;
-		const T tn = tail_norm * fabs(hinv);
-		tau = (T) 0.5 * ((T) 1 + tn * tn);
-		scale_tail = true;
-	}
+	T head = s_bc[0], hinv;
+	bool negligible;
+	const T tau = lv2_householder<T>(head, tail_norm, hinv, negligible);
+	const bool scale_tail = !negligible;
 	const T u1 = upd ? s_bc[2] : (T) 0, y1n = upd ? s_bc[1] : (T) 0;
 #pragma unroll
 	for (int e = 0; e < LV2_E; ++e) {
@@ -396,10 +395,7 @@ template <typename T> __global__ __launch_bounds__(LV2_NT) void td_step_kernel(c
 {
 	if (blockIdx.x > 0) { // helper block: the sums of index block blockIdx.x - 1 of pass k - 1
 		td_sum_block<T>(a, a.k - 1, (int) blockIdx.x - 1);
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		__syncthreads();
-		if (threadIdx.x == 0)
-			__hip_atomic_store(a.flags + (blockIdx.x - 1), (xwg_u64) a.k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		lv2_helper_done(a.flags + (blockIdx.x - 1), (xwg_u64) a.k);
 		return;
 	}
 	if (a.n - a.k - 1 <= LV2_E * LV2_NT && !a.force_mem)
@@ -586,20 +582,7 @@ static __device__ __forceinline__ void bd_sum_block(const double *part, int np, 
 	if (e >= len)
 		return;
 	const double *src = part + off + e;
-	double s0 = 0.0;
-	int p = 0;
-	for (; p + 8 <= np; p += 8) {
-		double v[8];
-#pragma unroll
-		for (int u = 0; u < 8; ++u)
-			v[u] = src[(size_t) (p + u) * stride];
-#pragma unroll
-		for (int u = 0; u < 8; ++u)
-			s0 += v[u];
-	}
-	for (; p < np; ++p)
-		s0 += src[(size_t) p * stride];
-	xwg_store(out + off + e, s0);
+	xwg_store(out + off + e, lv2_sum_shares(src, np, stride));
 }
 // which = 0: z sums of row pass k - 1 for bd_pre_kernel(k) (rows k .., column blocks of BR_TC); 1: y sums of column pass k for
 // bd_mid_kernel(k) (columns k + 1 .., row blocks of BC_TR)
@@ -613,10 +596,7 @@ template <typename T> static __device__ __forceinline__ void bd_helper(const BdA
 template <typename T> static __device__ __forceinline__ void bd_helper_block(const BdArgs<T> &a, int which)
 {
 	bd_helper<T>(a, which, (int) blockIdx.x - 1);
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	__syncthreads();
-	if (threadIdx.x == 0)
-		__hip_atomic_store((which == 0 ? a.zflag : a.yflag) + (blockIdx.x - 1), (xwg_u64) (a.k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	lv2_helper_done((which == 0 ? a.zflag : a.yflag) + (blockIdx.x - 1), (xwg_u64) (a.k + 1));
 }
 // block 0: the sums are complete (or it adds the shares itself if the helpers' flags do not come)
 template <typename T> static __device__ __forceinline__ void bd_wait_sums(const BdArgs<T> &a, int which)
@@ -669,18 +649,14 @@ template <typename T> static __device__ __forceinline__ void bd_pre_body(const B
 			a.z[i] = zf;
 			const T v = old - (u * y1 + zf);
 			at(i, k) = v;
-			nacc[0] += (v * sml) * (v * sml);
-			nacc[1] += v * v;
-			nacc[2] += (v * big) * (v * big);
+			LV2_NORM_ACC(nacc, v, sml, big);
 		}
 		for (int j = k + 1 + tid; j < n; j += LV2_NT)
 			at(k, j) -= up0 * a.y[j] + z1 * at(k - 1, j);
 	} else {
 		for (int i = 1 + tid; i < m; i += LV2_NT) {
 			const T v = at(i, 0);
-			nacc[0] += (v * sml) * (v * sml);
-			nacc[1] += v * v;
-			nacc[2] += (v * big) * (v * big);
+			LV2_NORM_ACC(nacc, v, sml, big);
 		}
 	}
 	// ---- (ii) left reflector of column k (:99-102)
@@ -768,9 +744,7 @@ template <typename T> static __device__ __forceinline__ void bd_pre_body_reg(con
 	for (int e = 0; e < LV2_E; ++e)
 		if (k + 1 + tid + e * LV2_NT < m) {
 			const T v = cold[e];
-			nacc[0] += (v * sml) * (v * sml);
-			nacc[1] += v * v;
-			nacc[2] += (v * big) * (v * big);
+			LV2_NORM_ACC(nacc, v, sml, big);
 		}
 	// ---- (ii) left reflector of column k (:99-102)
 	double accd[3] = {(double) nacc[0], (double) nacc[1], (double) nacc[2]};
@@ -834,9 +808,7 @@ template <typename T> static __device__ __forceinline__ void bd_mid_body_reg(con
 			yv[e] = (yv[e] + v[e]) * tl_inv;
 			a.y[j] = yv[e];
 			v[e] = v[e] - yv[e];
-			nacc[0] += (v[e] * sml) * (v[e] * sml);
-			nacc[1] += v[e] * v[e];
-			nacc[2] += (v[e] * big) * (v[e] * big);
+			LV2_NORM_ACC(nacc, v[e], sml, big);
 		}
 	}
 	double accd[3] = {(double) nacc[0], (double) nacc[1], (double) nacc[2]};
@@ -852,9 +824,7 @@ template <typename T> static __device__ __forceinline__ void bd_mid_body_reg(con
 				v[e] *= norm_inv;
 			a.vrow[j] = v[e]; // (v) multiplies by the normalised row as it is BEFORE the right reflector touches it
 			if (j >= k + 2) {
-				tacc[0] += (v[e] * sml) * (v[e] * sml);
-				tacc[1] += v[e] * v[e];
-				tacc[2] += (v[e] * big) * (v[e] * big);
+				LV2_NORM_ACC(tacc, v[e], sml, big);
 			}
 		}
 	}
@@ -988,9 +958,7 @@ template <typename T> static __device__ __forceinline__ void bd_mid_body(const B
 		a.y[j] = yv;
 		const T v = row(j) - yv;
 		row(j) = v;
-		nacc[0] += (v * sml) * (v * sml);
-		nacc[1] += v * v;
-		nacc[2] += (v * big) * (v * big);
+		LV2_NORM_ACC(nacc, v, sml, big);
 	}
 	double accd[3] = {(double) nacc[0], (double) nacc[1], (double) nacc[2]};
 	block_sum<LV2_NT, 3>(accd, s_part, s_red);
@@ -1005,9 +973,7 @@ template <typename T> static __device__ __forceinline__ void bd_mid_body(const B
 		}
 		a.vrow[j] = v; // (v) multiplies by the normalised row as it is BEFORE the right reflector touches it
 		if (j >= k + 2) {
-			tacc[0] += (v * sml) * (v * sml);
-			tacc[1] += v * v;
-			tacc[2] += (v * big) * (v * big);
+			LV2_NORM_ACC(tacc, v, sml, big);
 		}
 	}
 	if (k + 1 >= a.size)
@@ -1229,17 +1195,13 @@ template <typename T> static __device__ __forceinline__ void hs_pre_body(const H
 			const T v = at(i, k) - (u * y1 + zi); // column k: A21 -= u2 y1 + z2
 			at(i, k) = v;
 			if (i >= k + 2) {
-				nacc[0] += (v * sml) * (v * sml);
-				nacc[1] += v * v;
-				nacc[2] += (v * big) * (v * big);
+				LV2_NORM_ACC(nacc, v, sml, big);
 			}
 		}
 	} else {
 		for (int i = 2 + tid; i < n; i += LV2_NT) {
 			const T v = at(i, 0);
-			nacc[0] += (v * sml) * (v * sml);
-			nacc[1] += v * v;
-			nacc[2] += (v * big) * (v * big);
+			LV2_NORM_ACC(nacc, v, sml, big);
 		}
 	}
 	if (k + 1 >= n)
@@ -1320,9 +1282,7 @@ template <typename T> static __device__ __forceinline__ void hs_pre_body_reg(con
 		const int i = k + tid + e * LV2_NT;
 		if (i < n && i >= k + 2) {
 			const T v = ck[e];
-			nacc[0] += (v * sml) * (v * sml);
-			nacc[1] += v * v;
-			nacc[2] += (v * big) * (v * big);
+			LV2_NORM_ACC(nacc, v, sml, big);
 		}
 	}
 	if (k + 1 >= n)
@@ -1359,21 +1319,7 @@ template <typename T> __global__ __launch_bounds__(LV2_NT) void hs_pre_kernel(co
 		if (i >= k)
 			return;
 		const int np = (a.n - (k - 1) + TF_TC - 1) / TF_TC;
-		const double *src = a.wpart + i;
-		double s0 = 0.0;
-		int p = 0;
-		for (; p + 8 <= np; p += 8) {
-			double v[8];
-#pragma unroll
-			for (int u = 0; u < 8; ++u)
-				v[u] = src[(size_t) (p + u) * a.n];
-#pragma unroll
-			for (int u = 0; u < 8; ++u)
-				s0 += v[u];
-		}
-		for (; p < np; ++p)
-			s0 += src[(size_t) p * a.n];
-		a.dwp[i] = (T) s0 * ((T) 1 / a.taus[k - 1]);
+		a.dwp[i] = (T) lv2_sum_shares(a.wpart + i, np, (size_t) a.n) * ((T) 1 / a.taus[k - 1]);
 		return;
 	}
 	if (a.n - a.k <= LV2_E * LV2_NT && !a.force_mem)
@@ -1478,20 +1424,7 @@ template <typename T> __global__ __launch_bounds__(TF_NT) void hs_top_kernel(con
 		const bool isz = e >= r;
 		const int np = isz ? (r + TF_TC - 1) / TF_TC : (r + TF_TR - 1) / TF_TR;
 		const double *src = (isz ? a.zpart : a.ypart) + (k + 1) + (isz ? e - r : e);
-		double s0 = 0.0;
-		int p = 0;
-		for (; p + 8 <= np; p += 8) {
-			double v[8];
-#pragma unroll
-			for (int u = 0; u < 8; ++u)
-				v[u] = src[(size_t) (p + u) * n];
-#pragma unroll
-			for (int u = 0; u < 8; ++u)
-				s0 += v[u];
-		}
-		for (; p < np; ++p)
-			s0 += src[(size_t) p * n];
-		(isz ? a.zsum : a.ysum)[(k + 1) + (isz ? e - r : e)] = (T) s0;
+		(isz ? a.zsum : a.ysum)[(k + 1) + (isz ? e - r : e)] = (T) lv2_sum_shares(src, np, (size_t) n);
 		return;
 	}
 	const bool upd = k > 0;

@@ -3,8 +3,8 @@ columns / rows it touches in registers (at most 4096 remaining rows: every size 
 takes over above.  faer_hip_debug_level2_force_memory_bodies(1) runs the second one at every size: both restate the same expressions with
 the same block reductions; the compiler contracts multiply-adds differently in the two bodies, so the outputs agree to rounding (a few
 n eps ||A||, the bound of the oracle comparisons; fp64 tridiagonalization: bit for bit) -- which keeps the path that only matrices beyond
-4096 rows reach under test -- and one case beyond 4096 rows crosses the switch-over inside a factorization and is checked through the
-reference's property (evd/tridiag.rs:538-600: a similarity keeps the spectrum)."""
+4096 rows reach under test -- and three cases beyond 4096 rows cross the switch-over inside a factorization and are checked through the
+reference's properties (evd/tridiag.rs:538-600: a similarity keeps the spectrum; svd/bidiag.rs:380-440: the singular values are kept)."""
 import numpy as np
 import pytest
 
@@ -125,3 +125,32 @@ def test_tridiag_across_the_switch_over_n4400():
     ev_t = eigvalsh_tridiagonal(d, e)
     ev_a = np.linalg.eigvalsh(a)
     assert np.abs(ev_a - ev_t).max() <= 64 * EPS[np.dtype(np.float64)] * n * np.abs(a).max()
+
+
+def test_bidiag_across_the_switch_over_4200x200():
+    """m - k - 1 > 4096 for k < 103: bd_pre_kernel runs its memory-resident body there and the register body after, bd_mid_kernel (199 columns
+    at most) the register body throughout -- both residences alternate inside one column step; the singular values are kept"""
+    F = init_gpu()
+    m, n = 4200, 200
+    a = np.asarray(np.random.default_rng(4200).standard_normal((m, n)), dtype=np.float64, order="F")
+    vd = to_dev(a)
+    hl, hr = to_dev(np.zeros((8, n), dtype=np.float64, order="F")), to_dev(np.zeros((8, n - 1), dtype=np.float64, order="F"))
+    F.bidiag_in_place(vd, hl, hr)
+    b = np.array(to_host(vd))
+    bd = np.diag(np.diag(b)[:n]) + np.diag(np.diag(b, 1)[:n - 1], 1)
+    sv = np.linalg.svd(a, compute_uv=False)
+    assert np.abs(np.linalg.svd(bd, compute_uv=False) - sv).max() <= 64 * m * EPS[np.dtype(np.float64)] * sv[0]
+
+
+def test_hessenberg_across_the_switch_over_n4200():
+    """n - k > 4096 for k < 104: memory-resident body of hs_pre_kernel, then the register body; a unitary similarity keeps the Frobenius norm
+    and the trace of the Hessenberg part"""
+    F = init_gpu()
+    n = 4200
+    a = np.asarray(np.random.default_rng(4211).standard_normal((n, n)), dtype=np.float64, order="F")
+    vd, hd = to_dev(a), to_dev(np.zeros((8, n - 1), dtype=np.float64, order="F"))
+    F.hessenberg_in_place(vd, hd)
+    hs = np.triu(np.array(to_host(vd)), -1)
+    fro, tr = np.linalg.norm(a), np.trace(a)
+    assert abs(np.linalg.norm(hs) - fro) <= 64 * n * EPS[np.dtype(np.float64)] * fro
+    assert abs(np.trace(hs) - tr) <= 64 * n * EPS[np.dtype(np.float64)] * fro
