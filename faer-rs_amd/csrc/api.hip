@@ -1461,6 +1461,10 @@ size_t faer_hip_debug_llt_plan(size_t n, size_t tail_rows, size_t nb2, size_t *s
 		starts[i] = (size_t) J[i];
 	return J.size();
 }
+size_t faer_hip_debug_llt_steps(size_t n, size_t la_min, size_t tail_rows, size_t side_rmin, size_t dpanel_rmin, int *codes, size_t cap)
+{
+	return llt_debug_steps((idx_t) n, (idx_t) la_min, (idx_t) tail_rows, (idx_t) side_rmin, (idx_t) dpanel_rmin, codes, cap);
+}
 void faer_hip_debug_dump_timing(void)
 {
 	trsm_dump_timing();

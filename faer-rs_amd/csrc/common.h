@@ -361,6 +361,7 @@ template <typename T> long full_piv_lu_dev(MatV<T> A, idx_t *row_perm, idx_t *ro
 template <typename T> long colpiv_qr_dev(MatV<T> A, MatV<T> H, idx_t *col_perm, idx_t *col_perm_inv);
 // pure host planning logic, exported for the CPU tests (faer_hip_debug_*)
 std::vector<idx_t> llt_plan(idx_t n, idx_t tail_rows, idx_t nb2);
+size_t llt_debug_steps(idx_t n, idx_t la_min, idx_t tail_rows, idx_t side_rmin, idx_t dpanel_rmin, int *codes, size_t cap);
 int lu_leaf_width(idx_t m, int elem_bytes, int resident_workgroups);
 bool dist_two_streams_ok(idx_t panel_rows, int elem_bytes, int panel_cus, int all_cus);
 void lu_force_general(int on); // debug: every LU leaf on the non-cooperative path

@@ -281,28 +281,72 @@ __global__ __launch_bounds__(LDS_NT) void potrf_leaf_kernel(T *A, idx_t rs, idx_
 #endif
 }
 
-template <typename T>
-static void potrf_rec(MatV<T> A, int regularize, T eps, T delta, int *status, idx_t offset, T *Wbase, bool need_inv)
+// What the levels of one factorization share: regularisation rule, device status word, the packed images of the diagonal blocks
+template <typename T> struct CholWork {
+	int regularize;
+	T eps, delta;
+	int *status;			    // [0] first failing global column + 1, [1] regularisation count
+	T *Wbase;			    // one image per 128-block
+	idx_t wblk0 = 0;		    // the 128-block whose image is slot 0 (potrf_panel_dev: the panel's first one)
+	const signed char *signs = nullptr; // LDLT: expected pivot signs (null: none given)
+	T *Dv = nullptr;		    // LDLT: the pivots
+	// the image of the 128-block that starts at global column j
+	T *wslot(idx_t j) const { return Wbase + (size_t) (j / POTRF_NB - wblk0) * TriPack<T>::SIZE; }
+};
+
+// the leaf on the diagonal block D (<= 128 columns, at global column `offset`); W: where its packed image goes (null: no
+// solve will read it).  The LLT leaves are kernel class 5 of the profile, the LDLT leaf is not profiled.
+template <typename T, bool LDLT> static void chol_leaf(MatV<T> D, idx_t offset, T *W, const CholWork<T> &wk)
+{
+	ProfScope prof(LDLT ? -1 : 5, (double) D.nrows);
+	hipLaunchKernelGGL((potrf_leaf_kernel<T, LDLT>), dim3(1), dim3(LDS_NT), 0, ctx().stream, D.p, D.rs, D.cs, (int) D.nrows, wk.regularize,
+			   wk.eps, wk.delta, wk.status, (int) offset, W, wk.signs, wk.Dv);
+	FH_HIP(hipGetLastError());
+}
+
+// X[:, k] /= d[k]  (LDLT: A10 <- L10 = A10 D0^-1, cholesky/ldlt/factor.rs:447-455)
+template <typename T> __global__ void scale_cols_recip_kernel(T *X, idx_t rs, idx_t cs, idx_t m, idx_t n, const T *__restrict__ d)
+{
+	const idx_t total = m * n;
+	for (idx_t e = (idx_t) blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (idx_t) gridDim.x * blockDim.x) {
+		const idx_t i = e % m, k = e / m;
+		X[i * rs + k * cs] *= (T) 1 / d[k];
+	}
+}
+
+// Recursion by halves, for L L^T and for L D L^T (unit lower L, diagonal D, no pivoting: cholesky/ldlt/factor.rs:367-498 with
+// is_llt == false).  LDLT differs in the leaf, and in that the panel solve -- against the unit
+// triangles -- leaves L10 D0: A10 is then scaled by 1 / D0 (:447-455) and the trailing update is the diagonally weighted
+// product of the spicy_matmul surface (:456-470), lower(A11) -= L10 D0 L10^T.
+template <typename T, bool LDLT> static void chol_rec(MatV<T> A, const CholWork<T> &wk, idx_t offset, bool need_inv)
 {
 	const idx_t n = A.nrows;
 	if (n == 0)
 		return;
 	if (n <= POTRF_NB) {
-		T *W = need_inv ? Wbase + (size_t) (offset / POTRF_NB) * TriPack<T>::SIZE : nullptr;
-		ProfScope prof(5, (double) n);
-		hipLaunchKernelGGL((potrf_leaf_kernel<T, false>), dim3(1), dim3(LDS_NT), 0, ctx().stream, A.p, A.rs, A.cs, (int) n, regularize,
-				   eps, delta, status, (int) offset, W, (const signed char *) nullptr, (T *) nullptr);
-		FH_HIP(hipGetLastError());
+		chol_leaf<T, LDLT>(A, offset, need_inv ? wk.wslot(offset) : nullptr, wk);
 		return;
 	}
 	const idx_t h = ((n / 2 + POTRF_NB - 1) / POTRF_NB) * POTRF_NB;
 	MatV<T> A00 = A.sub(0, 0, h, h), A10 = A.sub(h, 0, n - h, h), A11 = A.sub(h, h, n - h, n - h);
-	potrf_rec<T>(A00, regularize, eps, delta, status, offset, Wbase, true);
+	chol_rec<T, LDLT>(A00, wk, offset, true);
 	// A10 <- A10 L00^-T, expressed like the reference (cholesky/ldlt/factor.rs:422-426) as L00 \ A10^T
-	trsm_lower_pre_dev<T>(A00.c(), A10.t(), Wbase + (size_t) (offset / POTRF_NB) * TriPack<T>::SIZE);
-	// lower(A11) -= A10 A10^T  (cholesky/ldlt/factor.rs:436-446 -> triangular.rs:602 DstKind::Lower)
-	gemm_dev<T>(A11, DST_LOWER, true, A10.c(), A10.t().c(), (T) -1);
-	potrf_rec<T>(A11, regularize, eps, delta, status, offset + h, Wbase, need_inv);
+	trsm_lower_pre_dev<T>(A00.c(), A10.t(), wk.wslot(offset));
+	GemmExtra<T> ex;
+	if constexpr (LDLT) {
+		const idx_t total = (n - h) * h;
+		idx_t blocks = (total + 255) / 256;
+		if (blocks > 65536)
+			blocks = 65536;
+		hipLaunchKernelGGL(scale_cols_recip_kernel<T>, dim3((unsigned) blocks), dim3(256), 0, ctx().stream, A10.p, A10.rs, A10.cs, n - h, h,
+				   wk.Dv + offset);
+		FH_HIP(hipGetLastError());
+		ex.diag = wk.Dv + offset;
+		ex.diag_stride = 1;
+	}
+	// lower(A11) -= A10 [D0] A10^T  (cholesky/ldlt/factor.rs:436-446 -> triangular.rs:602 DstKind::Lower)
+	gemm_dev<T>(A11, DST_LOWER, true, A10.c(), A10.t().c(), (T) -1, LDLT ? &ex : nullptr);
+	chol_rec<T, LDLT>(A11, wk, offset + h, need_inv);
 }
 
 // Factorization of a tall panel P (R x w, R >= w; the top w x w block is the diagonal block) in 128-column blocks -- three
@@ -318,20 +362,14 @@ static void potrf_rec(MatV<T> A, int regularize, T eps, T delta, int *status, id
 // trapezoids are 12-25 us.  Measured (profiles/r05_exp_llt_driver.txt): N = 16384 34.7-35.0 -> 34.0-34.1 ms, N = 8192 10.4-11.5
 // -> 9.6-9.7 ms; with the cheaper diagonal chains the look-ahead steps beat the sequential tail down to 1024 rows: 33.2 ms.
 template <typename T, typename AfterBlock>
-static void potrf_panel_flat_hook(MatV<T> P, int regularize, T eps, T delta, int *status, idx_t offset, T *Wbase, idx_t wblk0, AfterBlock after_block)
+static void potrf_panel_flat_hook(MatV<T> P, const CholWork<T> &wk, idx_t offset, AfterBlock after_block)
 {
-	// the inverse of the 128-block starting at global column offset + c0 goes to slot (offset + c0) / 128 - wblk0 of Wbase
 	const idx_t R = P.nrows, w = P.ncols;
 	for (idx_t c0 = 0; c0 < w; c0 += POTRF_NB) {
 		const idx_t nb = POTRF_NB < w - c0 ? POTRF_NB : w - c0;
-		T *W = Wbase + (size_t) ((offset + c0) / POTRF_NB - wblk0) * TriPack<T>::SIZE;
+		T *W = wk.wslot(offset + c0);
 		MatV<T> D = P.sub(c0, c0, nb, nb);
-		{
-			ProfScope prof(5, (double) nb);
-			hipLaunchKernelGGL((potrf_leaf_kernel<T, false>), dim3(1), dim3(LDS_NT), 0, ctx().stream, D.p, D.rs, D.cs, (int) nb, regularize, eps,
-					   delta, status, (int) (offset + c0), W, (const signed char *) nullptr, (T *) nullptr);
-		}
-		FH_HIP(hipGetLastError());
+		chol_leaf<T, false>(D, offset + c0, W, wk);
 		if (R > c0 + nb) // rows below <- rows below * L_kk^-T: substitution leaf, lanes along the rows of the panel
 			trsm_lower_pre_dev<T>(D.c(), P.sub(c0 + nb, c0, R - c0 - nb, nb).t(), W);
 		after_block(c0, nb, W); // (block column c0 of L is final, the packed image of its diagonal block is in W)
@@ -341,14 +379,13 @@ static void potrf_panel_flat_hook(MatV<T> P, int regularize, T eps, T delta, int
 		}
 	}
 }
-template <typename T>
-static void potrf_panel_flat(MatV<T> P, int regularize, T eps, T delta, int *status, idx_t offset, T *Wbase, idx_t wblk0 = 0)
+template <typename T> static void potrf_panel_flat(MatV<T> P, const CholWork<T> &wk, idx_t offset)
 {
-	potrf_panel_flat_hook<T>(P, regularize, eps, delta, status, offset, Wbase, wblk0, [](idx_t, idx_t, T *) {});
+	potrf_panel_flat_hook<T>(P, wk, offset, [](idx_t, idx_t, T *) {});
 }
 
 // Right-looking driver with look-ahead for large matrices: steps of LA_NB columns,
-//     [panel stream]  D_k = chol(A_kk)                         (recursive driver above; latency bound, few CUs)
+//     [panel stream]  D_k = chol(A_kk)                         (flat panel above; latency bound, few CUs)
 //     [bulk stream]   P_k = A_{>k,k} L_kk^-T                   (in place: substitution leaves + MFMA products)
 //     [bulk stream]   A_{k+1,k+1} -= P_k[0] P_k[0]^T           -> releases D_{k+1} on the panel stream
 //     [bulk stream]   rest of the trailing matrix -= P_k P_k^T (K = LA_NB: compute bound)
@@ -356,33 +393,32 @@ static void potrf_panel_flat(MatV<T> P, int regularize, T eps, T delta, int *sta
 // the trailing update of the previous step on CUs reserved for them (Ctx::lookahead_streams), instead of
 // leaving 255 CUs idle.  Same arithmetic per entry as the reference's right-looking sweep
 // (cholesky/ldlt/factor.rs:367-498) with a larger step.
+// LltPlan: the step table and the knobs; LltPlan::decide: what step k is; LltLookahead: one call, one method per kind of step.
 constexpr idx_t LA_NB = 1024;
-#ifndef LLT_SIDE_RMIN
-#define LLT_SIDE_RMIN 8192 // rows of the remaining lower square from which the panel solve runs on the side stream
-#endif
 
-// Step plan of the blocked driver (pure host logic, unit tested without a GPU through faer_hip_debug_llt_plan):
-// starts of the look-ahead panels; the last entry is where the sequential tail takes over.  The first step is LA_NB
-// wide, the following ones nb2 while at least 2 * nb2 rows remain behind them, LA_NB again towards the end; steps
-// stop once no more than `tail_rows` rows remain (or the next panel would reach the end of the matrix).
+// Step table of the blocked driver (pure host logic, unit tested without a GPU through faer_hip_debug_llt_plan):
+// starts of the look-ahead panels; the last entry is where the sequential tail takes over.  The first step is ONE 128-block,
+// the second 512 wide, the following ones nb2 while at least 2 * nb2 rows remain behind them, LA_NB again towards the end;
+// steps stop once no more than `tail_rows` rows remain (or the next panel would reach the end of the matrix).
+// (the driver runs nb2 = LA_NB: wider later steps -- K = nb2 trailing updates closer to the dense rate, fewer launch
+// boundaries -- measured no gain in round 2)
 std::vector<idx_t> llt_plan(idx_t n, idx_t tail_rows, idx_t nb2)
 {
 	// width of the first look-ahead step: the whole chip waits for the first diagonal block, so it is ONE 128-block (a
 	// leaf, ~55 us) instead of a 1024-wide one (~1.05 ms): 41.1 -> 40.1 ms at N = 16384
 	const idx_t first = POTRF_NB;
 	const idx_t second = 512; // (measured: 0 / 256 / 512: 33.54-33.56 / 33.34 / 33.21-33.30 ms at N = 16384)
-	std::vector<idx_t> J;
-	J.push_back(0);
+	std::vector<idx_t> J{0};
 	while (true) {
 		const idx_t j0 = J.back();
 		idx_t w = J.size() == 1 ? LA_NB : nb2;
 		if (n - j0 - w < 2 * w)
 			w = LA_NB; // narrow steps again towards the end
-		if (J.size() == 1 && first > 0 && first < w)
-			w = first; // (the whole chip waits for the first diagonal block)
+		if (J.size() == 1 && first < w)
+			w = first;
 		// the SECOND step: its diagonal chain + panel solve have only the K = `first` update of the whole matrix to hide
-		// behind (0.73 ms at N = 16384; a 1024-wide step needs 1.1 + 0.6 ms: the bulk stream idled 1.06 ms) -- LLT_SECOND wide
-		if (J.size() == 2 && first > 0 && second > 0 && second < w && n - j0 - second >= 2 * w)
+		// behind (0.73 ms at N = 16384; a 1024-wide step needs 1.1 + 0.6 ms: the bulk stream idled 1.06 ms)
+		if (J.size() == 2 && second < w && n - j0 - second >= 2 * w)
 			w = second;
 		if (!(n - j0 > tail_rows && j0 + w < n))
 			break;
@@ -391,215 +427,314 @@ std::vector<idx_t> llt_plan(idx_t n, idx_t tail_rows, idx_t nb2)
 	return J;
 }
 
-template <typename T>
-static void potrf_lookahead(MatV<T> A, int regularize, T eps, T delta, int *status, T *Wbase, hipStream_t caller)
+// How P_k, the rows below D_k, gets solved.
+enum class LltSolve {
+	// Round 4: the panel solve (a dependent chain of ~15 small launches, ~0.4 ms whatever the number of rows: 6.4 of the bulk
+	// stream's 34 ms, profiles/r03_llt_timeline.txt) does not sit between two trailing updates on the bulk stream: step k - 1
+	// had a plain side stream do it beside the square of its update (LltUpdate::Split), the bulk stream only waits for it.
+	OnSide,
+	// Round 5: the late steps.  Once the trailing products are shorter than the chains (fewer than side_rmin rows below the
+	// next panel) a step was the SUM of two chains: the diagonal block D_{k+1} on the panel stream (24 launches, 0.97 ms), then
+	// the solve of all of P_{k+1} on the bulk stream (15 launches, 0.41 ms), then the product of D_{k+2}: 1.48 ms per 1024
+	// columns with the trailing product hidden beside the first chain (kernel trace, profiles/r05_exp_llt_driver.txt).  But
+	// D_{k+2} needs only the TOP rows X0_{k+1} of P_{k+1} (the next diagonal block's rows), and those can be solved block column
+	// by block column right behind the leaves of D_{k+1}: a FOLLOWER on the side stream -- per 128-block one small product and one
+	// substitution leaf on w2 rows, behind an event of the leaf that produced the block's packed image -- finishes one block
+	// behind the diagonal chain.  The solve of the rows below X0 then runs on the bulk stream BESIDE the next diagonal chain.
+	// For the follower to start early the bulk stream brings X0's rows up to date in a launch of their own (and the diagonal
+	// block two steps ahead, which shares those rows) before the rest of the product (LltUpdate::BandMerged).
+	// Measured (profiles/r05_exp_llt_driver.txt): a late step 1.47 -> 1.36 ms, N = 16384 35.1-35.4 -> 34.9-35.0 ms -- less than the
+	// 0.4 ms per step the chains promise: the follower cannot start before the bulk stream has solved the rows that update X0
+	// (0.6 ms into the step), its small products run ~5 x slower beside the trailing product, and with the extra launches the
+	// bulk stream's own chain (solve 0.41 + four products) is now as long as the panel stream's.
+	Follower,
+	Bulk // all of it on the bulk stream behind D_k: the last step, when nothing was solved ahead
+};
+// How step k updates the trailing matrix.  Every kind but Last stands for one LltSolve of step k + 1 (LltPlan::decide).
+enum class LltUpdate {
+	Last,	    // one product on the whole trailing matrix; the tail driver takes over
+	Merged,	    // block column k + 1 below D_{k+1} + the lower square right of it in ONE launch (tri_skip)        -> Bulk
+	BandMerged, // the rows of X0_{k+1} and of D_{k+2} first (ONE band launch), then the merged product below them;
+		    // D_{k+1} is factored with a follower                                                            -> Follower
+	// Block column k + 1 FIRST (its own launch), and while the lower square right of it -- which neither reads nor writes
+	// that block column -- runs on the bulk stream, the side stream solves P_{k+1} = A_{>k+1,k+1} L_{k+1,k+1}^-T as soon as the
+	// panel stream has factored the diagonal block.  Its small kernels find their slots among the product's workgroups (the
+	// two launches are independent); it pays only while the square is much longer than the chain it hides.       -> OnSide
+	Split
+};
+// Where A_{k+1,k+1} -= X0 X0^T runs, X0 = the top rows of P_k.  (None <=> Last, WithFollower <=> LltSolve::Follower of the same
+// step: a follower step is never the last one, arrival() asks for k + 1 < nsteps.)
+enum class LltNextDiag {
+	None,	      // the last step has no next diagonal block
+	WithFollower, // on the bulk stream as soon as the follower has X0, before the rows below X0 are solved
+	OnPanel,      // on the panel stream: it has slack to spare while the trailing matrix is large, the bulk stream issues fewer launches
+	BulkFirst     // first launch of the update on the bulk stream
+};
+
+struct LltStep {
+	idx_t j0, j1, w, r; // panel columns [j0, j1), w of them; r rows below
+	idx_t w1, w2;	    // widths of the next two look-ahead panels (0: there is none)
+	LltSolve solve;
+	LltUpdate update;
+	LltNextDiag diag;
+	bool follower_next() const { return update == LltUpdate::BandMerged; } // D_{k+1} is factored with a follower
+};
+
+// The schedule of one blocked factorization: pure host data.  The knobs are read here and nowhere else (FAER_HIP_LLT_*: the
+// tests lower them to reach every kind of step at small sizes).
+// Once the remaining matrix is small the chain "diagonal block -> panel solve -> next diagonal block" is longer than the
+// trailing update it is meant to hide behind: below la_min and for the last tail_rows rows of a large matrix the steps run
+// back to back on the caller's stream (potrf_blocked).  Look-ahead pays from ~10k rows upwards (measured, N = 8192: 13.3 ms
+// sequential against 13.8 ms); round 5, right-looking diagonal chains: look-ahead from 8192 rows on -- 9.5 ms either way there,
+// 6144: 6.2 sequential against 6.5 -- and down to the last 1024 rows: tails of 4096 / 3072 / 2048 / 1024 rows 34.1 / 33.6-33.7 /
+// 33.4 / 33.2 ms at N = 16384.  side_rmin / dpanel_rmin re-swept with the right-looking chains: side solve from 4096 / 6144 / 8192 /
+// 10240 rows 33.7 / 33.0-33.2 / 33.1-33.6 / 33.6-34.0 ms, next diagonal block's product on the panel stream from 4096 / 8192 / 12288
+// rows 33.2 / 33.1-33.6 / 33.6-33.9: both left at 8192.
+struct LltPlan {
+	idx_t n, la_min, tail_rows; // smallest n on the blocked path; rows left to the sequential tail
+	idx_t side_rmin;	    // rows below a panel from which the side stream solves it
+	idx_t dpanel_rmin;	    // rows below panel k from which the update of D_{k+1} runs on the panel stream
+	std::vector<idx_t> J{0};    // look-ahead step k factors the columns [J[k], J[k + 1]); the tail starts at J.back()
+	LltPlan(idx_t n, idx_t la_min, idx_t tail_rows, idx_t side_rmin, idx_t dpanel_rmin)
+		: n(n), la_min(la_min), tail_rows(tail_rows), side_rmin(side_rmin), dpanel_rmin(dpanel_rmin)
+	{
+		if (blocked())
+			J = llt_plan(n, tail_rows, LA_NB);
+	}
+	static idx_t knob(const char *name, idx_t dflt) { return getenv(name) ? (idx_t) atol(getenv(name)) : dflt; }
+	explicit LltPlan(idx_t n)
+		: LltPlan(n, knob("FAER_HIP_LLT_LA_MIN", 2 * LA_NB), knob("FAER_HIP_LLT_TAIL", n < 8 * LA_NB ? n : LA_NB),
+			  knob("FAER_HIP_LLT_SIDE_RMIN", 8192), knob("FAER_HIP_LLT_DPANEL_RMIN", 8192)) {}
+	bool blocked() const { return n >= la_min && n > LA_NB; }
+	idx_t nsteps() const { return (idx_t) J.size() - 1; }
+	LltSolve arrival(idx_t k) const
+	{
+		if (k >= 1 && n - J[(size_t) k + 1] >= side_rmin)
+			return LltSolve::OnSide;
+		return k + 1 < nsteps() ? LltSolve::Follower : LltSolve::Bulk;
+	}
+	LltStep decide(idx_t k) const
+	{
+		const idx_t j0 = J[(size_t) k], j1 = J[(size_t) k + 1];
+		LltStep s{j0, j1, j1 - j0, n - j1, 0, 0, arrival(k), LltUpdate::Last, LltNextDiag::None};
+		if (k + 1 == nsteps())
+			return s;
+		s.w1 = J[(size_t) k + 2] - j1;
+		const LltSolve next = arrival(k + 1);
+		s.update = next == LltSolve::OnSide ? LltUpdate::Split : next == LltSolve::Follower ? LltUpdate::BandMerged : LltUpdate::Merged;
+		if (next == LltSolve::Follower) // (then k + 2 < nsteps: J[k + 3] exists)
+			s.w2 = J[(size_t) k + 3] - J[(size_t) k + 2];
+		s.diag = s.solve == LltSolve::Follower ? LltNextDiag::WithFollower : s.r >= dpanel_rmin ? LltNextDiag::OnPanel : LltNextDiag::BulkFirst;
+		return s;
+	}
+};
+// faer_hip_debug_llt_steps: the decisions of every look-ahead step as integers (the enums' values); the streams are assumed
+size_t llt_debug_steps(idx_t n, idx_t la_min, idx_t tail_rows, idx_t side_rmin, idx_t dpanel_rmin, int *codes, size_t cap)
 {
+	const LltPlan p(n, la_min, tail_rows, side_rmin, dpanel_rmin);
+	for (idx_t k = 0; k < p.nsteps() && (size_t) k < cap; ++k) {
+		const LltStep s = p.decide(k);
+		const int row[4] = {(int) s.solve, (int) s.update, (int) s.diag, (int) s.follower_next()};
+		std::copy(row, row + 4, codes + 4 * k);
+	}
+	return (size_t) p.nsteps();
+}
+
+template <typename T> struct LltLookahead {
+	MatV<T> A;
+	const CholWork<T> &wk;
+	const LltPlan &plan;
+	hipStream_t caller;
 	Ctx &c = ctx();
-	const idx_t n = A.nrows;
-	// Once the remaining matrix is small the chain "diagonal block -> panel solve -> next diagonal block" is longer
-	// than the trailing update it is meant to hide behind: the tail is factored on the caller's stream, whole chip,
-	// one tall panel (potrf_panel_flat) + ONE trailing update per step.
-	// Look-ahead pays from ~10k rows upwards (measured, N = 8192: 13.3 ms sequential against 13.8 ms); below that and
-	// for the last `tail_rows` rows of a large matrix the steps run back to back on the caller's stream.
-	// (round 5, right-looking diagonal chains: look-ahead from 8192 rows on -- 9.5 ms either way there, 6144: 6.2 sequential against
-	// 6.5 -- and down to the last 1024 rows: tails of 4096 / 3072 / 2048 / 1024 rows 34.1 / 33.6-33.7 / 33.4 / 33.2 ms at N = 16384)
-	const idx_t tail_rows = getenv("FAER_HIP_LLT_TAIL") ? atol(getenv("FAER_HIP_LLT_TAIL")) : (n < 8 * LA_NB ? n : LA_NB);
-	// Step widths of the look-ahead part: the FIRST step is LA_NB wide (its diagonal block is factored with the rest
-	// of the chip idle), the following ones LA_NB2 (wider steps: K = LA_NB2 trailing updates run closer to the dense
-	// rate and there are fewer launch boundaries per factorization) while at least 2 * LA_NB2 rows remain.
-	const idx_t nb2 = LA_NB; // (wider later steps measured no gain in round 2)
-	const std::vector<idx_t> J = llt_plan(n, tail_rows, nb2); // look-ahead steps: panel columns [J[k], J[k + 1])
-	idx_t ks = (idx_t) J.size() - 1; // look-ahead steps
-	if (ks > 0 && !c.lookahead_streams())
-		ks = 0;
-	const idx_t tail0 = ks > 0 ? J[(size_t) ks] : 0;
-	if (ks > 0) {
+	hipStream_t side = nullptr;
+	// across steps (what it says: who records it -> who waits for it):
+	hipEvent_t ev_diag = nullptr; // D_k is factored, its packed blocks are in wk: factor_diag, panel stream -> solve_bulk; side_solve of step k - 1
+	hipEvent_t ev_x0 = nullptr;   // X0_k is solved by the follower (implies ev_diag): factor_diag, side stream -> solve_follower
+	hipEvent_t ev_side = nullptr; // P_k is solved: side_solve of step k - 1 -> the bulk stream of step k (LltSolve::OnSide)
+	// inside a step, recorded on the bulk stream:
+	hipEvent_t ev_solved = nullptr; // P_k is solved -> the panel stream where it updates D_{k+1} itself (OnPanel)
+	hipEvent_t ev_col = nullptr;	// D_{k+1} is up to date (Split: all of block column k + 1) -> the panel stream otherwise; side_solve
+	hipEvent_t ev_band = nullptr;	// the rows of X0_{k+1} are up to date (BandMerged) -> the follower of D_{k+1}
+	hipEvent_t record(hipStream_t s)
+	{
+		hipEvent_t e = c.next_event();
+		FH_HIP(hipEventRecord(e, s));
+		return e;
+	}
+	MatV<T> panel(const LltStep &s) const { return A.sub(s.j1, s.j0, s.r, s.w); }		 // P_k
+	MatV<T> below_x0(const LltStep &s) const { return A.sub(s.j1 + s.w1, s.j0, s.r - s.w1, s.w); } // P_k without X0
+	MatV<const T> diag_block(const LltStep &s) const { return A.sub(s.j0, s.j0, s.w, s.w).c(); }
+	// D_k on the current (panel) stream, with the follower for X0_k if that panel is solved that way; the follower must not start
+	// before `rows_ready`: the rows of X0_k are up to date with panel k - 1 (null for the first panel)
+	void factor_diag(idx_t k, bool follower, hipEvent_t rows_ready)
+	{
+		const idx_t j0 = plan.J[(size_t) k], j1 = plan.J[(size_t) k + 1], w = j1 - j0;
+		MatV<T> D = A.sub(j0, j0, w, w);
+		if (!follower) {
+			potrf_panel_flat<T>(D, wk, j0);
+		} else {
+			MatV<T> X0 = A.sub(j1, j0, plan.J[(size_t) k + 2] - j1, w);
+			if (rows_ready)
+				stream_wait(side, rows_ready);
+			potrf_panel_flat_hook<T>(D, wk, j0, [&](idx_t c0, idx_t nb, T *W) {
+				hipEvent_t leaf = record(c.la_panel);
+				StreamScope ss(side);
+				stream_wait(side, leaf);
+				follow_block(D, X0, c0, nb, W);
+			});
+			ev_x0 = record(side);
+		}
+		ev_diag = record(c.la_panel);
+	}
+	// the follower behind the leaf of block column c0 of D.  RIGHT-looking on the rows of X0: solve block column c0, then take it
+	// out of the block columns right of it (K = 128 products: ~15 us each; the left-looking form with K = c0 on w1 x 128 outputs
+	// took ~100 us per block and the follower finished 0.34 ms behind the diagonal chain -- kernel trace r5v29)
+	void follow_block(MatV<T> D, MatV<T> X0, idx_t c0, idx_t nb, const T *W)
+	{
+		const idx_t w = D.ncols, w1 = X0.nrows, c1 = c0 + nb;
+		trsm_lower_pre_dev<T>(D.sub(c0, c0, nb, nb).c(), X0.sub(0, c0, w1, nb).t(), W);
+		if (c1 < w)
+			gemm_dev<T>(X0.sub(0, c1, w1, w - c1), DST_FULL, true, X0.sub(0, c0, w1, nb).c(), D.sub(c1, c0, w - c1, nb).t().c(), (T) -1);
+	}
+	// A_{k+1,k+1} -= X0 X0^T on the current stream
+	void update_next_diag(const LltStep &s)
+	{
+		MatV<const T> X0 = panel(s).sub(0, 0, s.w1, s.w).c();
+		gemm_dev<T>(A.sub(s.j1, s.j1, s.w1, s.w1), DST_LOWER, true, X0, X0.t(), (T) -1);
+	}
+
+	// X0_k came from the follower: the next diagonal block at once (-> the panel stream), then the rows below X0_k
+	void solve_follower(const LltStep &s)
+	{
+		stream_wait(c.la_bulk, ev_x0);
+		update_next_diag(s);
+		ev_col = record(c.la_bulk);
+		if (s.r > s.w1)
+			trsm_lower_pre_dev<T>(diag_block(s), below_x0(s).t(), wk.wslot(s.j0));
+	}
+	// P_k <- P_k L_kk^-T in place (cholesky/ldlt/factor.rs:422-426): the reference's TRSM recursion on the 128-blocks of
+	// L_kk -- substitution leaves against the packed diagonal blocks the panel stream left in wk, MFMA products in between
+	void solve_bulk(const LltStep &s)
+	{
+		stream_wait(c.la_bulk, ev_diag);
+		trsm_lower_pre_dev<T>(diag_block(s), panel(s).t(), wk.wslot(s.j0));
+	}
+
+	// the trailing matrix, one method per LltUpdate
+	void update_last(const LltStep &s)
+	{
+		MatV<const T> X = panel(s).c();
+		gemm_dev<T>(A.sub(s.j1, s.j1, s.r, s.r), DST_LOWER, true, X, X.t(), (T) -1);
+	}
+	void update_merged(const LltStep &s)
+	{
+		if (s.diag == LltNextDiag::BulkFirst) {
+			update_next_diag(s);
+			ev_col = record(c.la_bulk);
+		}
+		GemmExtra<T> ex;
+		ex.tri_skip = s.w1;
+		if (s.update == LltUpdate::BandMerged) {
+			// the rows of X0_{k+1} (the follower of the next diagonal block waits for them) and, in the same rows, the
+			// diagonal block two steps ahead; the merged product below then skips these rows as well
+			// (ONE launch: the rows [w1, w1 + w2) of the lower triangle of the leading (w1 + w2)^2 block)
+			const idx_t wb = s.w1 + s.w2;
+			MatV<const T> X01 = panel(s).sub(0, 0, wb, s.w).c();
+			gemm_dev<T>(A.sub(s.j1, s.j1, wb, wb), DST_LOWER, true, X01, X01.t(), (T) -1, &ex);
+			ev_band = record(c.la_bulk);
+			ex.tri_skip = wb;
+		}
+		// block column k + 1 below its diagonal block + the remaining lower square in ONE launch: the lower triangle of the
+		// whole trailing matrix minus its leading rows
+		MatV<const T> X = panel(s).c();
+		if (ex.tri_skip < s.r)
+			gemm_dev<T>(A.sub(s.j1, s.j1, s.r, s.r), DST_LOWER, true, X, X.t(), (T) -1, &ex);
+	}
+	void update_split(const LltStep &s)
+	{
+		if (s.diag == LltNextDiag::BulkFirst)
+			update_next_diag(s);
+		const idx_t jc = s.j1 + s.w1, rc = s.r - s.w1;
+		MatV<const T> X2 = below_x0(s).c();
+		// block column k + 1 below its diagonal block
+		gemm_dev<T>(A.sub(jc, s.j1, rc, s.w1), DST_FULL, true, X2, panel(s).sub(0, 0, s.w1, s.w).c().t(), (T) -1);
+		ev_col = record(c.la_bulk);
+		// the remaining lower square
+		gemm_dev<T>(A.sub(jc, jc, rc, rc), DST_LOWER, true, X2, X2.t(), (T) -1);
+	}
+	// P_{k+1} on the side stream beside the square of update_split
+	void side_solve(const LltStep &s)
+	{
+		StreamScope sc(side);
+		stream_wait(side, ev_col);
+		stream_wait(side, ev_diag);
+		trsm_lower_pre_dev<T>(A.sub(s.j1, s.j1, s.w1, s.w1).c(), A.sub(s.j1 + s.w1, s.j1, s.r - s.w1, s.w1).t(), wk.wslot(s.j1));
+		ev_side = record(side);
+	}
+
+	void run()
+	{
 		c.reset_events();
-		hipEvent_t e0 = c.next_event();
-		FH_HIP(hipEventRecord(e0, caller));
+		hipEvent_t e0 = record(caller);
 		stream_wait(c.la_bulk, e0);
 		stream_wait(c.la_panel, e0);
-		hipEvent_t ev_diag; // D_k factored (its packed 128-blocks are in Wbase)
 		c.qr_side_streams();
-		hipStream_t side = c.qr_side[0];
-		// Round 5: the late steps.  Once the trailing products are shorter than the chains (fewer than LLT_SIDE_RMIN rows below the
-		// next panel) a step was the SUM of two chains: the diagonal block D_{k+1} on the panel stream (24 launches, 0.97 ms), then
-		// the solve of all of P_{k+1} on the bulk stream (15 launches, 0.41 ms), then the product of D_{k+2}: 1.48 ms per 1024
-		// columns with the trailing product hidden beside the first chain (kernel trace, profiles/r05_exp_llt_driver.txt).  But
-		// D_{k+2} needs only the TOP rows X0_{k+1} of P_{k+1} (the next diagonal block's rows), and those can be solved block column
-		// by block column right behind the leaves of D_{k+1}: a FOLLOWER on the side stream -- per 128-block one small product and one
-		// substitution leaf on w2 rows, behind an event of the leaf that produced the block's packed image -- finishes one block
-		// behind the diagonal chain.  The solve of the rows below X0 then runs on the bulk stream BESIDE the next diagonal chain.
-		// For the follower to start early the bulk stream brings X0's rows up to date in a launch of their own (and the diagonal
-		// block two steps ahead, which shares those rows) before the rest of the product.
-		// Measured (profiles/r05_exp_llt_driver.txt): a late step 1.47 -> 1.36 ms, N = 16384 35.1-35.4 -> 34.9-35.0 ms -- less than the
-		// 0.4 ms per step the chains promise: the follower cannot start before the bulk stream has solved the rows that update X0
-		// (0.6 ms into the step), its small products run ~5 x slower beside the trailing product, and with the extra launches the
-		// bulk stream's own chain (solve 0.41 + four products) is now as long as the panel stream's.
-		// (re-swept with the right-looking chains: side solve from 4096 / 6144 / 8192 / 10240 rows 33.7 / 33.0-33.2 / 33.1-33.6 / 33.6-34.0 ms,
-		// next diagonal block's product on the panel stream from 4096 / 8192 / 12288 rows 33.2 / 33.1-33.6 / 33.6-33.9: both left at 8192)
-		const idx_t side_rmin = LLT_SIDE_RMIN, dpanel_rmin = 8192;
-		const bool x_follow = true;
-		auto rows_below = [&](idx_t kk) { return n - J[(size_t) kk + 1]; };
-		auto solved_on_side = [&](idx_t kk) { return kk >= 1 && rows_below(kk) >= side_rmin; }; // (decided in step kk - 1)
-		auto follow = [&](idx_t kk) { return x_follow && kk + 1 < ks && !solved_on_side(kk); };
-		hipEvent_t ev_x0 = nullptr;     // X0_k solved by the follower (implies D_k factored)
-		hipEvent_t ev_x0upd = nullptr;  // the rows of X0_{k+1} are up to date with panel k (bulk stream)
-		// D_kk on the current (panel) stream, with the follower for X0_kk if that panel is solved that way
-		auto factor_diag = [&](idx_t kk, hipEvent_t x0upd) {
-			const idx_t jj0 = J[(size_t) kk], jj1 = J[(size_t) kk + 1], ww = jj1 - jj0;
-			MatV<T> D = A.sub(jj0, jj0, ww, ww);
-			if (!follow(kk)) {
-				potrf_panel_flat<T>(D, regularize, eps, delta, status, jj0, Wbase);
-			} else {
-				const idx_t ww1 = J[(size_t) kk + 2] - jj1;
-				MatV<T> X0f = A.sub(jj1, jj0, ww1, ww);
-				bool first = true;
-				potrf_panel_flat_hook<T>(D, regularize, eps, delta, status, jj0, Wbase, 0, [&](idx_t c0, idx_t nb, T *W) {
-					hipEvent_t el = c.next_event();
-					FH_HIP(hipEventRecord(el, c.la_panel));
-					StreamScope ss(side);
-					if (first && x0upd)
-						stream_wait(side, x0upd);
-					first = false;
-					stream_wait(side, el);
-					// RIGHT-looking on these rows: solve block column c0, then take it out of the block columns right of it
-					// (K = 128 products: ~15 us each; the left-looking form with K = c0 on w1 x 128 outputs took ~100 us per block
-					// and the follower finished 0.34 ms behind the diagonal chain -- kernel trace r5v29)
-					trsm_lower_pre_dev<T>(A.sub(jj0 + c0, jj0 + c0, nb, nb).c(), X0f.sub(0, c0, ww1, nb).t(), W);
-					const idx_t c1 = c0 + nb;
-					if (c1 < ww)
-						gemm_dev<T>(X0f.sub(0, c1, ww1, ww - c1), DST_FULL, true, X0f.sub(0, c0, ww1, nb).c(), A.sub(jj0 + c1, jj0 + c0, ww - c1, nb).t().c(), (T) -1);
-				});
-				ev_x0 = c.next_event();
-				FH_HIP(hipEventRecord(ev_x0, side));
-			}
-			ev_diag = c.next_event();
-			FH_HIP(hipEventRecord(ev_diag, c.la_panel));
-		};
+		side = c.qr_side[0];
 		{
 			StreamScope sc(c.la_panel);
-			factor_diag(0, nullptr);
+			factor_diag(0, plan.arrival(0) == LltSolve::Follower, nullptr);
 		}
-		// trailing size from which the update of the next diagonal block runs on the panel stream (it has slack to
-		// spare while the trailing matrix is large, and the bulk stream then issues fewer launches per step)
-		// Round 4: the panel solve of step k + 1 (a dependent chain of ~15 small launches, ~0.4 ms whatever the number of rows:
-		// 6.4 of the bulk stream's 34 ms, profiles/r03_llt_timeline.txt) no longer sits between two trailing updates on the bulk
-		// stream.  Update k brings block column k + 1 up to date FIRST (its own launch), and while the rest of update k -- the
-		// lower square right of it, which neither reads nor writes that block column -- runs on the bulk stream, a plain side
-		// stream solves P_{k+1} = A_{>k+1,k+1} L_{k+1,k+1}^-T as soon as the panel stream has factored the diagonal block.
-		// Its small kernels find their slots among the product's workgroups (the two launches are independent); towards the
-		// end, where the rest of the update is shorter than the chain, the chain is exposed as before.
-		hipEvent_t ev_solved = nullptr; // P_k solved (recorded on the stream that did it)
-		for (idx_t k = 0; k < ks; ++k) {
-			const idx_t j0 = J[(size_t) k], j1 = J[(size_t) k + 1], w = j1 - j0; // panel columns [j0, j1)
-			const idx_t r = n - j1;						       // rows below
-			const bool last = k + 1 == ks;					       // the tail driver takes over after this step
-			const idx_t w1 = last ? 0 : J[(size_t) k + 2] - j1;		       // width of the next look-ahead panel
-			MatV<T> Pk = A.sub(j1, j0, r, w);
-			MatV<const T> X = Pk.c(), X0 = Pk.sub(0, 0, w1, w).c();
-			const bool fol_k = follow(k), fol_n = !last && follow(k + 1);
-			const bool d_on_panel = !last && dpanel_rmin > 0 && r >= dpanel_rmin && !fol_k;
-			// (the side-stream solve pays only while the rest of the update is much longer than the chain it hides)
-			const bool side_solve = !last && r - w1 >= side_rmin;
-			hipEvent_t ev_upd, ev_col = nullptr;
+		for (idx_t k = 0; k < plan.nsteps(); ++k) {
+			const LltStep s = plan.decide(k);
 			{
 				StreamScope sc(c.la_bulk);
-				if (ev_solved) {
-					stream_wait(c.la_bulk, ev_solved);
-				} else if (fol_k) {
-					// X0_k came from the follower: the next diagonal block at once (-> the panel stream), then the rows below X0_k
-					stream_wait(c.la_bulk, ev_x0);
-					gemm_dev<T>(A.sub(j1, j1, w1, w1), DST_LOWER, true, X0, X0.t(), (T) -1);
-					ev_col = c.next_event();
-					FH_HIP(hipEventRecord(ev_col, c.la_bulk));
-					if (r > w1)
-						trsm_lower_pre_dev<T>(A.sub(j0, j0, w, w).c(), Pk.sub(w1, 0, r - w1, w).t(), Wbase + (size_t) (j0 / POTRF_NB) * TriPack<T>::SIZE);
-				} else {
-					stream_wait(c.la_bulk, ev_diag);
-					// P_k <- P_k L_kk^-T in place (cholesky/ldlt/factor.rs:422-426): the reference's TRSM recursion on the
-					// 128-blocks of L_kk -- substitution leaves against the packed diagonal blocks the panel stream
-					// left in Wbase, MFMA products in between
-					trsm_lower_pre_dev<T>(A.sub(j0, j0, w, w).c(), Pk.t(), Wbase + (size_t) (j0 / POTRF_NB) * TriPack<T>::SIZE);
-				}
-				ev_upd = c.next_event(); // P_k is solved
-				FH_HIP(hipEventRecord(ev_upd, c.la_bulk));
-				if (last) {
-					gemm_dev<T>(A.sub(j1, j1, r, r), DST_LOWER, true, X, X.t(), (T) -1);
-				} else if (!side_solve) {
-					if (!d_on_panel && !fol_k) { // next diagonal block first
-						gemm_dev<T>(A.sub(j1, j1, w1, w1), DST_LOWER, true, X0, X0.t(), (T) -1);
-						ev_col = c.next_event();
-						FH_HIP(hipEventRecord(ev_col, c.la_bulk));
-					}
-					GemmExtra<T> ex;
-					ex.tri_skip = w1;
-					ev_x0upd = nullptr;
-					if (fol_n) {
-						// the rows of X0_{k+1} (the follower of the next diagonal block waits for them) and, in the same rows, the
-						// diagonal block two steps ahead; the merged product below then skips these rows as well
-						// (ONE launch: the rows [w1, w1 + w2) of the lower triangle of the leading (w1 + w2)^2 block)
-						const idx_t w2 = J[(size_t) k + 3] - J[(size_t) k + 2];
-						MatV<const T> X01 = Pk.sub(0, 0, w1 + w2, w).c();
-						GemmExtra<T> exb;
-						exb.tri_skip = w1;
-						gemm_dev<T>(A.sub(j1, j1, w1 + w2, w1 + w2), DST_LOWER, true, X01, X01.t(), (T) -1, &exb);
-						ev_x0upd = c.next_event();
-						FH_HIP(hipEventRecord(ev_x0upd, c.la_bulk));
-						ex.tri_skip = w1 + w2;
-					}
-					// block column k+1 below its diagonal block + the remaining lower square in ONE launch: the lower
-					// triangle of the whole trailing matrix minus its leading rows
-					if (ex.tri_skip < r)
-						gemm_dev<T>(A.sub(j1, j1, r, r), DST_LOWER, true, X, X.t(), (T) -1, &ex);
-				} else {
-					ev_x0upd = nullptr;
-					if (!d_on_panel && !fol_k) // next diagonal block first (a follower step has done it above)
-						gemm_dev<T>(A.sub(j1, j1, w1, w1), DST_LOWER, true, X0, X0.t(), (T) -1);
-					// block column k + 1 below its diagonal block
-					gemm_dev<T>(A.sub(j1 + w1, j1, r - w1, w1), DST_FULL, true, Pk.sub(w1, 0, r - w1, w).c(), X0.t(), (T) -1);
-					ev_col = c.next_event();
-					FH_HIP(hipEventRecord(ev_col, c.la_bulk));
-					// the remaining lower square
-					MatV<const T> X2 = Pk.sub(w1, 0, r - w1, w).c();
-					gemm_dev<T>(A.sub(j1 + w1, j1 + w1, r - w1, r - w1), DST_LOWER, true, X2, X2.t(), (T) -1);
-				}
+				if (s.solve == LltSolve::OnSide)
+					stream_wait(c.la_bulk, ev_side);
+				else if (s.solve == LltSolve::Follower)
+					solve_follower(s);
+				else
+					solve_bulk(s);
+				ev_solved = record(c.la_bulk);
+				if (s.update == LltUpdate::Last)
+					update_last(s);
+				else if (s.update == LltUpdate::Split)
+					update_split(s);
+				else
+					update_merged(s);
 			}
-			ev_solved = nullptr;
-			if (!last) {
-				{
-					StreamScope sc(c.la_panel);
-					stream_wait(c.la_panel, d_on_panel ? ev_upd : ev_col);
-					if (d_on_panel)
-						gemm_dev<T>(A.sub(j1, j1, w1, w1), DST_LOWER, true, X0, X0.t(), (T) -1);
-					// (the follower of D_{k+1} must not start before X0_{k+1}'s rows are up to date with panel k: in the steps that
-					// solve on the side stream the whole block column is updated before ev_col, in the late steps ev_x0upd says so)
-					factor_diag(k + 1, fol_n ? (ev_x0upd ? ev_x0upd : ev_col) : nullptr);
-				}
-				if (side_solve) {
-					StreamScope sc(side);
-					stream_wait(side, ev_col);
-					stream_wait(side, ev_diag);
-					trsm_lower_pre_dev<T>(A.sub(j1, j1, w1, w1).c(), A.sub(j1 + w1, j1, r - w1, w1).t(), Wbase + (size_t) (j1 / POTRF_NB) * TriPack<T>::SIZE);
-					ev_solved = c.next_event();
-					FH_HIP(hipEventRecord(ev_solved, side));
-				}
+			if (s.update == LltUpdate::Last) // (it starts nothing on the panel or the side stream)
+				break;
+			{
+				StreamScope sc(c.la_panel);
+				stream_wait(c.la_panel, s.diag == LltNextDiag::OnPanel ? ev_solved : ev_col);
+				if (s.diag == LltNextDiag::OnPanel)
+					update_next_diag(s);
+				// (the follower of D_{k+1} must not start before X0_{k+1}'s rows are up to date with panel k: ev_band says so)
+				factor_diag(k + 1, s.follower_next(), s.follower_next() ? ev_band : nullptr);
 			}
+			if (s.update == LltUpdate::Split)
+				side_solve(s);
 		}
-		if (ev_solved) // (cannot happen: the last look-ahead step starts no solve; kept for symmetry)
-			stream_wait(caller, ev_solved);
-		// rejoin the caller's stream
-		hipEvent_t eb = c.next_event(), ep = c.next_event();
-		FH_HIP(hipEventRecord(eb, c.la_bulk));
-		FH_HIP(hipEventRecord(ep, c.la_panel));
+		// rejoin the caller's stream (the side stream's last launch was waited for by the bulk stream)
+		hipEvent_t eb = record(c.la_bulk), ep = record(c.la_panel);
 		stream_wait(caller, eb);
 		stream_wait(caller, ep);
 	}
-	// ---- tail (everything, if the matrix is small): sequential, whole chip
-	// (steps of 128 / 256 / 512 / 2048 columns here: 34.2-34.3 / 34.3 / 34.4-34.5 ms at N = 16384 against 34.0-34.1; N = 8192: 10.4 / 9.7 / 9.6 / 9.8 against 9.65)
-	for (idx_t j0 = tail0; j0 < n; j0 += LA_NB) {
+};
+
+// The blocked driver: the look-ahead steps of the plan, then the tail (everything, if there are no steps) -- sequential, whole
+// chip, on the caller's stream: one tall panel (potrf_panel_flat) + ONE trailing update per step.
+// (steps of 128 / 256 / 512 / 2048 columns here: 34.2-34.3 / 34.3 / 34.4-34.5 ms at N = 16384 against 34.0-34.1; N = 8192: 10.4 / 9.7 / 9.6 / 9.8 against 9.65)
+template <typename T> static void potrf_blocked(MatV<T> A, const CholWork<T> &wk, LltPlan plan)
+{
+	const idx_t n = A.nrows;
+	if (plan.nsteps() > 0 && !ctx().lookahead_streams())
+		plan.J.resize(1); // (without the look-ahead streams everything is the tail)
+	if (plan.nsteps() > 0)
+		LltLookahead<T>{A, wk, plan, ctx().stream}.run();
+	for (idx_t j0 = plan.J.back(); j0 < n; j0 += LA_NB) {
 		const idx_t w = LA_NB < n - j0 ? LA_NB : n - j0, R = n - j0;
-		potrf_panel_flat<T>(A.sub(j0, j0, R, w), regularize, eps, delta, status, j0, Wbase);
+		potrf_panel_flat<T>(A.sub(j0, j0, R, w), wk, j0);
 		if (R > w) {
 			MatV<const T> P2 = A.sub(j0 + w, j0, R - w, w).c();
 			gemm_dev<T>(A.sub(j0 + w, j0 + w, R - w, R - w), DST_LOWER, true, P2, P2.t(), (T) -1);
@@ -618,10 +753,32 @@ template <typename T> void potrf_panel_dev(MatV<T> P, T reg_delta, T reg_eps, in
 	const idx_t nblk = (P.ncols + POTRF_NB - 1) / POTRF_NB;
 	Scratch winv((size_t) nblk * TriPack<T>::BYTES);
 	const int regularize = (reg_delta > (T) 0 && reg_eps > (T) 0) ? 1 : 0;
-	potrf_panel_flat<T>(P, regularize, reg_eps, reg_delta, status_dev, offset, winv.as<T>(), offset / POTRF_NB);
+	potrf_panel_flat<T>(P, CholWork<T>{regularize, reg_eps, reg_delta, status_dev, winv.as<T>(), offset / POTRF_NB}, offset);
 }
 template void potrf_panel_dev<double>(MatV<double>, double, double, int *, idx_t);
 template void potrf_panel_dev<float>(MatV<float>, float, float, int *, idx_t);
+
+// What a whole factorization (LLT or LDLT) sets up and reads back: the zeroed status word, one packed image per diagonal block (only
+// those some TRSM will use are filled), the regularisation rule (cholesky/llt/factor.rs:85-86, cholesky/ldlt/factor.rs:766-767)
+template <typename T> struct CholCall {
+	Scratch st{64}, winv;
+	CholWork<T> wk;
+	CholCall(idx_t n, T reg_delta, T reg_eps)
+		: winv(n > POTRF_NB ? (size_t) ((n + POTRF_NB - 1) / POTRF_NB) * TriPack<T>::BYTES : 256),
+		  wk{(reg_delta > (T) 0 && reg_eps > (T) 0) ? 1 : 0, reg_eps, reg_delta, st.as<int>(), winv.as<T>()}
+	{
+		FH_HIP(hipMemsetAsync(wk.status, 0, 64, ctx().stream));
+	}
+	// the one synchronisation of the call; >= 0: regularisation count, < 0: -(index + 1) of the failing pivot
+	long finish()
+	{
+		int h[2] = {0, 0};
+		FH_HIP(hipMemcpyAsync(h, wk.status, sizeof(h), hipMemcpyDeviceToHost, ctx().stream));
+		ctx().sync();
+		ctx().quiesce();
+		return h[0] != 0 ? -(long) h[0] : (long) h[1];
+	}
+};
 
 template <typename T> long potrf_lower_dev(MatV<T> A, T reg_delta, T reg_eps)
 {
@@ -629,25 +786,13 @@ template <typename T> long potrf_lower_dev(MatV<T> A, T reg_delta, T reg_eps)
 	FH_CHECK(A.nrows < (1L << 30), "potrf: matrix too large");
 	if (A.nrows == 0)
 		return 0;
-	const idx_t n = A.nrows;
-	Scratch st(64);
-	int *status = st.as<int>();
-	FH_HIP(hipMemsetAsync(status, 0, 64, ctx().stream));
-	// one 128 x 128 inverse per diagonal block (only the blocks that some TRSM will use are filled)
-	const idx_t nblk = (n + POTRF_NB - 1) / POTRF_NB;
-	Scratch winv(n > POTRF_NB ? (size_t) nblk * TriPack<T>::BYTES : 256);
-	const int regularize = (reg_delta > (T) 0 && reg_eps > (T) 0) ? 1 : 0; // cholesky/llt/factor.rs:85-86
-	// FAER_HIP_LLT_LA_MIN / FAER_HIP_LLT_TAIL: thresholds of the blocked driver (tests lower them to reach every
-	// code path at small sizes)
-	const idx_t la_min = getenv("FAER_HIP_LLT_LA_MIN") ? atol(getenv("FAER_HIP_LLT_LA_MIN")) : 2 * LA_NB;
-	if (n >= la_min && n > LA_NB)
-		potrf_lookahead<T>(A, regularize, reg_eps, reg_delta, status, winv.as<T>(), ctx().stream);
+	CholCall<T> call(A.nrows, reg_delta, reg_eps);
+	const LltPlan plan(A.nrows);
+	if (plan.blocked())
+		potrf_blocked<T>(A, call.wk, plan);
 	else
-		potrf_rec<T>(A, regularize, reg_eps, reg_delta, status, 0, winv.as<T>(), false);
-	int h[2] = {0, 0};
-	FH_HIP(hipMemcpyAsync(h, status, sizeof(h), hipMemcpyDeviceToHost, ctx().stream));
-	ctx().sync();
-	ctx().quiesce();
+		chol_rec<T, false>(A, call.wk, 0, false);
+	const long ret = call.finish();
 #ifdef FH_LEAF_TIMING
 	{
 		unsigned long long d[8];
@@ -656,64 +801,10 @@ template <typename T> long potrf_lower_dev(MatV<T> A, T reg_delta, T reg_eps)
 			d[0], d[1], d[2], d[3], d[4], d[5]);
 	}
 #endif
-	if (h[0] != 0)
-		return -(long) h[0]; // -(index + 1)
-	return (long) h[1];
+	return ret;
 }
 
-// ------------------------------------------------------------------------------------------------
-// L D L^T (unit lower L, diagonal D; no pivoting) -- cholesky/ldlt/factor.rs:367-498 with is_llt == false,
-// SURVEY.md section 8f item 1.  Same recursion by halves and the same leaf; the panel solve is the unit-lower
-// TRSM against the leaf inverses, then A10 is scaled by 1/D0 (:447-455) and the trailing update is the
-// diagonally weighted product of the spicy_matmul surface (:456-470): lower(A11) -= L10 D0 L10^T.
-// ------------------------------------------------------------------------------------------------
-template <typename T> __global__ void scale_cols_recip_kernel(T *X, idx_t rs, idx_t cs, idx_t m, idx_t n, const T *__restrict__ d)
-{
-	const idx_t total = m * n;
-	for (idx_t e = (idx_t) blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (idx_t) gridDim.x * blockDim.x) {
-		const idx_t i = e % m, k = e / m;
-		X[i * rs + k * cs] *= (T) 1 / d[k];
-	}
-}
-
-template <typename T>
-static void sytrf_rec(MatV<T> A, int regularize, T eps, T delta, int *status, idx_t offset, T *Wbase, bool need_inv, const signed char *signs,
-		      T *Dv)
-{
-	const idx_t n = A.nrows;
-	if (n == 0)
-		return;
-	if (n <= POTRF_NB) {
-		T *W = need_inv ? Wbase + (size_t) (offset / POTRF_NB) * TriPack<T>::SIZE : nullptr;
-		hipLaunchKernelGGL((potrf_leaf_kernel<T, true>), dim3(1), dim3(LDS_NT), 0, ctx().stream, A.p, A.rs, A.cs, (int) n, regularize, eps,
-				   delta, status, (int) offset, W, signs, Dv);
-		FH_HIP(hipGetLastError());
-		return;
-	}
-	const idx_t h = ((n / 2 + POTRF_NB - 1) / POTRF_NB) * POTRF_NB;
-	MatV<T> A00 = A.sub(0, 0, h, h), A10 = A.sub(h, 0, n - h, h), A11 = A.sub(h, h, n - h, n - h);
-	sytrf_rec<T>(A00, regularize, eps, delta, status, offset, Wbase, true, signs, Dv);
-	// A10 <- A10 L00^-T (unit lower; the leaf inverses were taken of the unit triangles) = L10 D0
-	trsm_lower_pre_dev<T>(A00.c(), A10.t(), Wbase + (size_t) (offset / POTRF_NB) * TriPack<T>::SIZE);
-	// A10 <- L10 = A10 D0^-1
-	{
-		const idx_t total = (n - h) * h;
-		idx_t blocks = (total + 255) / 256;
-		if (blocks > 65536)
-			blocks = 65536;
-		hipLaunchKernelGGL(scale_cols_recip_kernel<T>, dim3((unsigned) blocks), dim3(256), 0, ctx().stream, A10.p, A10.rs, A10.cs, n - h, h,
-				   Dv + offset);
-		FH_HIP(hipGetLastError());
-	}
-	// lower(A11) -= L10 D0 L10^T
-	GemmExtra<T> ex;
-	ex.diag = Dv + offset;
-	ex.diag_stride = 1;
-	gemm_dev<T>(A11, DST_LOWER, true, A10.c(), A10.t().c(), (T) -1, &ex);
-	sytrf_rec<T>(A11, regularize, eps, delta, status, offset + h, Wbase, need_inv, signs, Dv);
-}
-
-// returns >= 0: regularization count, < 0: -(index + 1) of the zero pivot.  `signs_host`: n int8 or NULL.
+// L D L^T (chol_rec<T, true>).  `signs_host`: n int8 or NULL.
 template <typename T> long sytrf_lower_dev(MatV<T> A, T reg_delta, T reg_eps, const signed char *signs_host)
 {
 	FH_CHECK(A.nrows == A.ncols, "ldlt: matrix must be square");
@@ -721,26 +812,15 @@ template <typename T> long sytrf_lower_dev(MatV<T> A, T reg_delta, T reg_eps, co
 	if (A.nrows == 0)
 		return 0;
 	const idx_t n = A.nrows;
-	Scratch st(64);
-	int *status = st.as<int>();
-	FH_HIP(hipMemsetAsync(status, 0, 64, ctx().stream));
-	const idx_t nblk = (n + POTRF_NB - 1) / POTRF_NB;
-	Scratch winv(n > POTRF_NB ? (size_t) nblk * TriPack<T>::BYTES : 256);
+	CholCall<T> call(n, reg_delta, reg_eps);
 	Scratch dv((size_t) n * sizeof(T)), sg((size_t) n + 256);
-	const int regularize = (reg_delta > (T) 0 && reg_eps > (T) 0) ? 1 : 0; // cholesky/ldlt/factor.rs:766-767
-	const signed char *signs = nullptr;
-	if (signs_host && regularize) {
+	call.wk.Dv = dv.as<T>();
+	if (signs_host && call.wk.regularize) {
 		FH_HIP(hipMemcpyAsync(sg.p, signs_host, (size_t) n, hipMemcpyHostToDevice, ctx().stream));
-		signs = sg.as<signed char>();
+		call.wk.signs = sg.as<signed char>();
 	}
-	sytrf_rec<T>(A, regularize, reg_eps, reg_delta, status, 0, winv.as<T>(), false, signs, dv.as<T>());
-	int h[2] = {0, 0};
-	FH_HIP(hipMemcpyAsync(h, status, sizeof(h), hipMemcpyDeviceToHost, ctx().stream));
-	ctx().sync();
-	ctx().quiesce();
-	if (h[0] != 0)
-		return -(long) h[0];
-	return (long) h[1];
+	chol_rec<T, true>(A, call.wk, 0, false);
+	return call.finish();
 }
 
 template long sytrf_lower_dev<double>(MatV<double>, double, double, const signed char *);

@@ -542,6 +542,15 @@ FAER_HIP_API void faer_hip_debug_stream_xcc(int which, int nblocks, unsigned *ou
  * blocked Cholesky (last entry = start of the sequential tail; returns the number of entries) and the leaf width
  * the cooperative LU panel kernel picks for `nrows` rows when `resident_workgroups` workgroups fit the device. */
 FAER_HIP_API size_t faer_hip_debug_llt_plan(size_t n, size_t tail_rows, size_t nb2, size_t *starts, size_t cap);
+/* ... and what each look-ahead step of that driver is, for the thresholds given (smallest n on the blocked path, rows left to the
+ * tail, rows below a panel from which it is solved on the side stream / from which the next diagonal block is updated on the panel
+ * stream; the look-ahead streams are assumed to exist).  Four codes per step k in codes[4 k ..]: how P_k gets solved (0 on the side
+ * stream by step k - 1, 1 top rows by the follower, 2 on the bulk stream), the trailing update (0 last, 1 merged, 2 band + merged,
+ * 3 block column then square beside the side-stream solve), where D_{k+1} is updated (0 nowhere: last, 1 on the bulk stream with
+ * the follower's rows, 2 on the panel stream, 3 first on the bulk stream), whether D_{k+1} is factored with a follower (0 / 1).
+ * Writes at most `cap` steps and returns their number. */
+FAER_HIP_API size_t faer_hip_debug_llt_steps(size_t n, size_t la_min, size_t tail_rows, size_t side_rmin, size_t dpanel_rmin, int *codes,
+					     size_t cap);
 FAER_HIP_API int faer_hip_debug_lu_leaf_width(size_t nrows, FaerHipDType dtype, int resident_workgroups);
 /* tests: run every leaf of the partial-pivot LU on the non-cooperative path (the fallback for panels taller than the
  * cooperative kernel can keep resident and for the rerun after an exchange timeout) */

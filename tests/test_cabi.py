@@ -76,8 +76,9 @@ def test_product_path_has_no_cpu_fallback():
 
 
 def test_driver_planning_logic_needs_no_gpu():
-    """host-side decisions of the device drivers (pure functions, csrc/potrf.hip llt_plan, csrc/getrf.hip
-    lu_leaf_width): step plan of the blocked Cholesky and the leaf shape of the cooperative LU panel"""
+    """host-side decisions of the device drivers (pure functions, csrc/potrf.hip llt_plan and LltPlan::decide, csrc/getrf.hip
+    lu_leaf_width): step plan of the blocked Cholesky, what each of its look-ahead steps is, and the leaf shape of the
+    cooperative LU panel"""
     F = fa()
     lib = F.lib()
     lib.faer_hip_debug_llt_plan.restype = C.c_size_t
@@ -103,6 +104,78 @@ def test_driver_planning_logic_needs_no_gpu():
             j = plan(n, tail)
             assert j[0] == 0 and all(b > a for a, b in zip(j, j[1:])) and j[-1] < n
             assert all((b - a) % 128 == 0 for a, b in zip(j, j[1:]))
+
+    # ---- what each look-ahead step of the blocked Cholesky is (csrc/potrf.hip LltPlan::decide): four codes per step
+    SIDE, FOLLOWER, BULK = 0, 1, 2  # how P_k gets solved: by step k - 1 on the side stream / top rows by the follower / bulk stream
+    LAST, MERGED, BAND, SPLIT = 0, 1, 2, 3  # trailing update: last / merged / band + merged / block column, then square
+    NONE, WITH_FOLLOWER, ON_PANEL, BULK_FIRST = 0, 1, 2, 3  # where the update of D_{k+1} runs
+    lib.faer_hip_debug_llt_steps.restype = C.c_size_t
+
+    def steps(n, tail, side, dpanel, la_min=2048):
+        buf = (C.c_int * (4 * 64))()
+        cnt = lib.faer_hip_debug_llt_steps(*(C.c_size_t(v) for v in (n, la_min, tail, side, dpanel)), buf, C.c_size_t(64))
+        assert cnt <= 64
+        return [tuple(buf[4 * k:4 * k + 4]) for k in range(cnt)]
+
+    def rules(n, tail, side, dpanel):
+        """the schedule written as the conditions the one-function driver used to evaluate per step"""
+        J = plan(n, tail)
+        ks = len(J) - 1
+        below = lambda k: n - J[k + 1]  # noqa: E731
+        solved_on_side = lambda k: k >= 1 and below(k) >= side  # noqa: E731
+        follow = lambda k: k + 1 < ks and not solved_on_side(k)  # noqa: E731
+        out = []
+        for k in range(ks):
+            last = k + 1 == ks
+            w1 = 0 if last else J[k + 2] - J[k + 1]
+            fol_k, fol_n = follow(k), (not last) and follow(k + 1)
+            d_on_panel = (not last) and below(k) >= dpanel and not fol_k
+            side_solve = (not last) and below(k) - w1 >= side
+            arrived = k >= 1 and out[-1][1] == SPLIT  # (the event of the previous step's side-stream solve is set)
+            solve = SIDE if arrived else FOLLOWER if fol_k else BULK
+            update = LAST if last else SPLIT if side_solve else BAND if fol_n else MERGED
+            diag = NONE if last else WITH_FOLLOWER if fol_k else ON_PANEL if d_on_panel else BULK_FIRST
+            out.append((solve, update, diag, int(fol_n)))
+        return J, out
+
+    # 1. the production schedule: N = 16384, default knobs (blocked from 2048, tail 1024, both thresholds 8192).
+    # Panels start at 0, 128, 640, then every 1024 up to 16000 (17 steps); rows below panel k: 16256, 15744, 14720, ... , 8576 (k = 8),
+    # 7552 (k = 9), ..., 1408 (k = 15), 384 (k = 16).  solved_on_side(k) = k >= 1 and below(k) >= 8192: k = 1 .. 8.
+    # follow(k) = k + 1 < 17 and not solved_on_side(k): k = 0 and k = 9 .. 15.  side_solve(k) = not last and below(k + 1) >= 8192:
+    # k = 0 .. 7.  d_on_panel(k) = not last and below(k) >= 8192 and not follow(k): k = 1 .. 8.  Hence:
+    #   k = 0        follower step; its update is split (P_1 is solved on the side stream); D_1 plain
+    #   k = 1 .. 7   P_k arrived from the side stream; split update; D_{k+1} updated on the panel stream, factored plain
+    #   k = 8        arrived from the side stream; side_solve(8) fails (7552 rows) and follow(9) holds: band + merged update, D_9 with
+    #                a follower, its update still on the panel stream (8576 rows)
+    #   k = 9 .. 14  follower steps: band + merged, D_{k+1} with a follower
+    #   k = 15       follower step; follow(16) fails (16 is the last step): merged update without the band, D_16 plain
+    #   k = 16       last; nothing was solved ahead: all of P_16 on the bulk stream
+    assert steps(16384, 1024, 8192, 8192) == (
+        [(FOLLOWER, SPLIT, WITH_FOLLOWER, 0)] + 7 * [(SIDE, SPLIT, ON_PANEL, 0)] + [(SIDE, BAND, ON_PANEL, 1)] +
+        6 * [(FOLLOWER, BAND, WITH_FOLLOWER, 1)] + [(FOLLOWER, MERGED, WITH_FOLLOWER, 0)] + [(BULK, LAST, NONE, 0)])
+    assert rules(16384, 1024, 8192, 8192)[1] == steps(16384, 1024, 8192, 8192)
+    assert steps(2047, 0, 8192, 8192) == [] and steps(1024, 0, 8192, 8192, la_min=512) == []  # not on the blocked path
+    # 2. the exclusions the enums are built on, and the old conditions themselves, over a grid of sizes and thresholds
+    for n in (2049, 3000, 5197, 10240, 16384, 20000):
+        for tail in (0, 1024, 4096):
+            for side in (1024, 2048, 3000, 8192):
+                for dpanel in (1024, 2048, 3000, 8192):
+                    J, want = rules(n, tail, side, dpanel)
+                    st = steps(n, tail, side, dpanel)
+                    assert st == want, (n, tail, side, dpanel)
+                    for k, (solve, update, diag, fol) in enumerate(st):
+                        if k >= 1:  # arrived from the side stream <=> the step before split its update
+                            assert (solve == SIDE) == (st[k - 1][1] == SPLIT)
+                        assert not (fol and update == SPLIT)  # no follower behind a split update
+                        assert (update == BAND) == bool(fol) and (update != BAND or k + 3 < len(J))  # the band needs J[k + 3]
+                        assert (update == LAST) == (k + 1 == len(st)) == (diag == NONE)
+                        assert (diag == WITH_FOLLOWER) == (solve == FOLLOWER)  # (a follower step is never the last one)
+    # 3. the small case of test_gpu_factor.py::test_llt_lookahead_step_kinds runs every kind of every decision
+    small = steps(5197, 0, 2048, 3000)
+    assert plan(5197, 0) == [0, 128, 640, 1664, 2688, 3712, 4736]
+    assert small == [(FOLLOWER, SPLIT, WITH_FOLLOWER, 0), (SIDE, SPLIT, ON_PANEL, 0), (SIDE, SPLIT, ON_PANEL, 0),
+                     (SIDE, BAND, BULK_FIRST, 1), (FOLLOWER, MERGED, WITH_FOLLOWER, 0), (BULK, LAST, NONE, 0)]
+    assert [{s[i] for s in small} for i in range(4)] == [{0, 1, 2}, {0, 1, 2, 3}, {0, 1, 2, 3}, {0, 1}]
 
     # LU leaf: 64 columns while ceil(rows / 512) workgroups are resident (fp64), narrower / taller shapes after that
     w = lambda rows, dt, cap: lib.faer_hip_debug_lu_leaf_width(C.c_size_t(rows), C.c_int(dt), cap)  # noqa: E731

@@ -141,20 +141,35 @@ def test_llt_full_size_property(oracle):
     assert d <= 64 * k * 2.3e-16 * np.abs(np.tril(ref)).max(), d
 
 
-@pytest.mark.parametrize("n,tail", [(4096, 0), (4363, 0), (5120 + 77, 2048), (5120 + 77, 1 << 20), (6144, 3000), (3072 + 5, 1024)])
-def test_llt_lookahead_path(n, tail, monkeypatch):
+# thresholds at which n = 5197 runs every kind of look-ahead step (pinned without a GPU by
+# test_cabi.py::test_driver_planning_logic_needs_no_gpu): panels at 0, 128, 640, 1664, 2688, 3712, 4736; step 0 follower + split
+# update, steps 1-2 solved on the side stream + split update + D_{k+1} updated on the panel stream, step 3 arrived from the side
+# stream + band and merged update + follower next, step 4 follower + merged update, step 5 last
+LLT_STEP_KINDS = {"FAER_HIP_LLT_SIDE_RMIN": "2048", "FAER_HIP_LLT_DPANEL_RMIN": "3000"}
+
+
+@pytest.mark.parametrize("n,tail,knobs,dtype", [pytest.param(n, tail, {}, "float64", id=f"{n}-{tail}") for n, tail in
+                                                [(4096, 0), (4363, 0), (5120 + 77, 2048), (5120 + 77, 1 << 20), (6144, 3000), (3072 + 5, 1024)]] +
+                         [pytest.param(5197, 0, LLT_STEP_KINDS, "float64", id="5197-0-step-kinds"),
+                          pytest.param(5197, 0, LLT_STEP_KINDS, "float32", id="5197-0-step-kinds-float32")])
+def test_llt_lookahead_path(n, tail, knobs, dtype, monkeypatch):
     """the blocked driver of large matrices (potrf.hip): look-ahead steps on two CU-masked streams (1024 columns
     each) followed by the sequential tail of tall left-looking panels; thresholds lowered through the environment
-    so that every mix (look-ahead only, both, tail only) and a ragged last step run at test sizes.  Entrywise
-    L L^T == A on the lower triangle, untouched strict upper triangle, same answer twice"""
+    so that every mix (look-ahead only, both, tail only), a ragged last step and (step-kinds) every kind of look-ahead
+    step run at test sizes; the driver is a template, so the last case runs once in fp32 with the bound in its eps.
+    Entrywise L L^T == A on the lower triangle, untouched strict upper triangle, same answer twice"""
     import torch
 
     F = init_gpu()
     monkeypatch.setenv("FAER_HIP_LLT_LA_MIN", "2048")
     monkeypatch.setenv("FAER_HIP_LLT_TAIL", str(tail))
+    for name, value in knobs.items():
+        monkeypatch.setenv(name, value)
+    dt = getattr(torch, dtype)
+    eps = 2.3e-16 if dtype == "float64" else 2.3e-16 * 2.0 ** 29  # (eps of fp32 = 2^29 eps of fp64)
     g = torch.Generator(device="cuda").manual_seed(n)
-    b = torch.randn((n, n), dtype=torch.float64, device="cuda", generator=g)
-    a = (b @ b.t() + n * torch.eye(n, dtype=torch.float64, device="cuda")).t()
+    b = torch.randn((n, n), dtype=dt, device="cuda", generator=g)
+    a = (b @ b.t() + n * torch.eye(n, dtype=dt, device="cuda")).t()
     marked = a.clone()
     iu = torch.triu_indices(n, n, 1, device="cuda")
     marked[iu[0], iu[1]] = -7.5
@@ -162,25 +177,29 @@ def test_llt_lookahead_path(n, tail, monkeypatch):
     assert F.llt_factor_in_place(l) == 0
     F.synchronize()
     assert (l[iu[0], iu[1]] == -7.5).all().item()
-    L = torch.tril(l)
-    err = (torch.tril(L @ L.t() - a)).abs().max().item()
-    assert err <= 32 * n * 2.3e-16 * a.abs().max().item()
+    L = torch.tril(l).double()  # (the check itself in fp64 whatever the factor's type)
+    err = (torch.tril(L @ L.t() - a.double())).abs().max().item()
+    assert err <= 32 * n * eps * a.abs().max().item()
     l2 = marked.clone()
     assert F.llt_factor_in_place(l2) == 0
     F.synchronize()
     assert torch.equal(l, l2)
 
 
-@pytest.mark.parametrize("tail", [0, 2500, 1 << 20])
-def test_llt_lookahead_failure_index(tail, monkeypatch):
-    """first non-positive pivot deep inside a later step of the blocked driver (look-ahead step / tail panel):
+@pytest.mark.parametrize("tail,knobs,bad", [(0, {}, 3333), (2500, {}, 3333), (1 << 20, {}, 3333), (0, LLT_STEP_KINDS, 2000)],
+                         ids=["0", "2500", "1048576", "0-side-stream-solve"])
+def test_llt_lookahead_failure_index(tail, knobs, bad, monkeypatch):
+    """first non-positive pivot deep inside a later step of the blocked driver (look-ahead step / tail panel / a look-ahead
+    step whose panel the side stream solves: column 2000 of n = 5000 lies in step 3, [1664, 2688), 2312 >= 2048 rows below it):
     same index as the definition"""
     import torch
 
     F = init_gpu()
     monkeypatch.setenv("FAER_HIP_LLT_LA_MIN", "2048")
     monkeypatch.setenv("FAER_HIP_LLT_TAIL", str(tail))
-    n, bad = 5000, 3333
+    for name, value in knobs.items():
+        monkeypatch.setenv(name, value)
+    n = 5000
     g = torch.Generator(device="cuda").manual_seed(5)
     b = torch.randn((n, n), dtype=torch.float64, device="cuda", generator=g)
     a = (b @ b.t() + n * torch.eye(n, dtype=torch.float64, device="cuda")).t().clone()
