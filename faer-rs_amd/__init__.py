@@ -93,6 +93,25 @@ class VecRef(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("len", C.c_size_t), ("stride", C.c_ssize_t)]
 
 
+class VecMut(VecRef):
+    pass
+
+
+class LbltParams(C.Structure):
+    """include/faer_hip.h FaerLbltParams {pivoting, par_threshold, block_size} (the ffi order)"""
+    _fields_ = [("pivoting", C.c_int), ("par_threshold", C.c_size_t), ("block_size", C.c_size_t)]
+
+
+class LbltStatus(C.Structure):
+    """include/faer_hip.h FaerLbltStatus: tag (0 Ok, 1 Unknown), then ok.transposition_count"""
+    _fields_ = [("tag", C.c_int), ("transposition_count", C.c_size_t)]
+
+
+# include/faer_hip.h FaerPivotingStrategy
+PIVOTING_PARTIAL, PIVOTING_PARTIAL_DIAG, PIVOTING_ROOK, PIVOTING_ROOK_DIAG, PIVOTING_FULL = 0, 1, 2, 3, 4
+PivotingStrategy = {"partial": 0, "partial_diag": 1, "rook": 2, "rook_diag": 3, "full": 4}
+
+
 class LdltError(Exception):
     """faer::linalg::cholesky::ldlt::factor::LdltError::ZeroPivot { index }"""
 
@@ -191,6 +210,11 @@ def lib():
                      "apply_householder_on_the_left_scratch", "apply_householder_transpose_on_the_left_scratch"):
             getattr(L, f"libfaer_v0_23_{name}_{suf}").restype = Layout
         getattr(L, f"faer_hip_dist_partial_piv_lu_{suf}").restype = PartialPivLuStatus
+        getattr(L, f"libfaer_v0_23_LbltParams_{suf}").restype = LbltParams
+        for it in ("u32", "u64"):
+            getattr(L, f"libfaer_v0_23_lblt_factor_in_place_{it}_{suf}").restype = LbltStatus
+            for name in ("lblt_factor_in_place_scratch", "lblt_solve_in_place_scratch", "lblt_reconstruct_scratch", "lblt_inverse_scratch"):
+                getattr(L, f"libfaer_v0_23_{name}_{it}_{suf}").restype = Layout
     L.libfaer_v0_23_get_global_par.restype = Par
     L.faer_hip_version.restype = C.c_char_p
     L.faer_hip_device_count.restype = C.c_int
@@ -939,6 +963,79 @@ def qr_inverse(out, qr, q_coeff, par=PAR_SEQ):
     return out
 
 
+def _vec(x, cls=VecRef):
+    """1-D numpy array / torch tensor -> VecRef/VecMut (stride in elements)"""
+    if _is_torch(x):
+        assert x.dim() == 1
+        return cls(x.data_ptr(), x.shape[0], x.stride(0))
+    assert x.ndim == 1
+    return cls(x.ctypes.data, x.shape[0], x.strides[0] // x.itemsize)
+
+
+def lblt_factor_in_place(a, subdiag=None, pivoting=None, index_dtype=np.uint64, par=PAR_SEQ):
+    """cholesky/bunch_kaufman/factor.rs:1161-1234: P A P^T = L B L^T of the symmetric matrix in the lower triangle of `a` (the strict
+    upper triangle is never touched).  Unit lower L strictly below the diagonal of `a`, the diagonal of B on it, the subdiagonal of
+    the 2 x 2 blocks in `subdiag` (created next to `a` when None).  pivoting: a PIVOTING_* constant (None: the default, PartialDiag).
+    returns (subdiag, perm_fwd, perm_bwd, transposition_count)"""
+    suf, _, _ = _dtype_suffix(a)
+    n = a.shape[0]
+    it = "u64" if np.dtype(index_dtype) == np.uint64 else "u32"
+    if subdiag is None:
+        if _is_torch(a):
+            import torch
+
+            subdiag = torch.zeros(n, dtype=a.dtype, device=a.device)
+        else:
+            subdiag = np.zeros(n, dtype=a.dtype)
+    fwd = np.zeros(n, dtype=index_dtype)
+    bwd = np.zeros(n, dtype=index_dtype)
+    L = lib()
+    params = getattr(L, f"libfaer_v0_23_LbltParams_{suf}")()
+    if pivoting is not None:
+        params.pivoting = int(pivoting)
+    st = getattr(L, f"libfaer_v0_23_lblt_factor_in_place_{it}_{suf}")(
+        _mat(a, MatMut), _vec(subdiag, VecMut), SliceMut(fwd.ctypes.data, n), SliceMut(bwd.ctypes.data, n), par, MemAlloc(None, 0), params)
+    if st.tag != 0:
+        raise RuntimeError("LbltStatus::Unknown")
+    return subdiag, fwd, bwd, st.transposition_count
+
+
+def _lblt_call(name, lb, diag, subdiag, perm_fwd, perm_bwd):
+    suf, _, _ = _dtype_suffix(lb)
+    it = "u64" if np.dtype(perm_fwd.dtype) == np.uint64 else "u32"
+    n = lb.shape[0]
+    d = _diag_vec(lb) if diag is None else _vec(diag)
+    return getattr(lib(), f"libfaer_v0_23_{name}_{it}_{suf}"), d, _vec(subdiag), SliceRef(perm_fwd.ctypes.data, n), SliceRef(perm_bwd.ctypes.data, n)
+
+
+def lblt_solve_in_place(lb, subdiag, perm_fwd, perm_bwd, rhs, diag=None, par=PAR_SEQ):
+    """cholesky/bunch_kaufman/solve.rs:35-104: rhs <- A^-1 rhs; `lb` as lblt_factor_in_place leaves it (diag None: its diagonal)"""
+    fn, d, s, pf, pb = _lblt_call("lblt_solve_in_place", lb, diag, subdiag, perm_fwd, perm_bwd)
+    fn(_mat(lb), d, s, C.c_int(CONJ_NO), pf, pb, _mat(rhs, MatMut), par, MemAlloc(None, 0))
+    return rhs
+
+
+def lblt_reconstruct(out, lb, subdiag, perm_fwd, perm_bwd, diag=None, par=PAR_SEQ):
+    """cholesky/bunch_kaufman/reconstruct.rs: lower(out) <- P^T L B L^T P"""
+    fn, d, s, pf, pb = _lblt_call("lblt_reconstruct", lb, diag, subdiag, perm_fwd, perm_bwd)
+    fn(_mat(out, MatMut), _mat(lb), d, s, pf, pb, par, MemAlloc(None, 0))
+    return out
+
+
+def lblt_inverse(out, lb, subdiag, perm_fwd, perm_bwd, diag=None, par=PAR_SEQ):
+    """cholesky/bunch_kaufman/inverse.rs: out <- A^-1 (the whole matrix)"""
+    fn, d, s, pf, pb = _lblt_call("lblt_inverse", lb, diag, subdiag, perm_fwd, perm_bwd)
+    fn(_mat(out, MatMut), _mat(lb), d, s, pf, pb, par, MemAlloc(None, 0))
+    return out
+
+
+def debug_lblt_last():
+    """(blocked panels, leaf rows, 2 x 2 pivots, host synchronisations inside panels) of this thread's last lblt_factor_in_place"""
+    out = (C.c_size_t * 4)()
+    lib().faer_hip_debug_lblt_last(out)
+    return tuple(int(v) for v in out)
+
+
 # ------------------------------------------------------------------ high level owners (faer/src/linalg/solvers.rs)
 def _empty_like_f(a, shape):
     if _is_torch(a):
@@ -998,6 +1095,25 @@ class Llt:
 
     def solve_in_place(self, rhs):
         return llt_solve_in_place(self.l, rhs)
+
+
+class Lblt:
+    """solvers.rs Lblt: copies the matrix, factors its lower triangle with the default strategy"""
+
+    def __init__(self, a, pivoting=None):
+        self.lb = _copy_f(a)
+        self.subdiag, self.perm, self.perm_inv, self.transposition_count = lblt_factor_in_place(self.lb, pivoting=pivoting)
+
+    def solve_in_place(self, rhs):
+        return lblt_solve_in_place(self.lb, self.subdiag, self.perm, self.perm_inv, rhs)
+
+    def reconstruct(self):
+        out = _empty_like_f(self.lb, self.lb.shape)
+        return lblt_reconstruct(out, self.lb, self.subdiag, self.perm, self.perm_inv)
+
+    def inverse(self):
+        out = _empty_like_f(self.lb, self.lb.shape)
+        return lblt_inverse(out, self.lb, self.subdiag, self.perm, self.perm_inv)
 
 
 class PartialPivLu:

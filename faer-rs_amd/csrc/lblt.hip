@@ -1,0 +1,949 @@
+// Bunch-Kaufman factorization P A P^T = L B L^T of a symmetric indefinite matrix (include/faer_hip.h section 2g;
+// faer/src/linalg/cholesky/bunch_kaufman/{factor,solve,reconstruct,inverse}.rs).  Only the lower triangle of A is read or
+// written.  Strategies Partial, PartialDiag, Rook and RookDiag; Full is a different level-2 algorithm and aborts.
+//
+//  * Leaf (lblt_leaf_kernel): one workgroup keeps a trailing block of at most 64 rows in LDS as a full symmetric image and runs the
+//    unblocked algorithm on it (factor.rs:784-902), rook loop included.  Every wavefront takes the pivot decisions redundantly from the
+//    same image, so a step costs barriers only around the swaps and the elimination.
+//  * Panel for more than 64 remaining rows (factor.rs:491-699, the W-panel algorithm): the trailing matrix is updated lazily.  Per pivot
+//    step a multi-workgroup column kernel forms one candidate column w = a(:, i) - A_l W_l[i, :]^T (symmetric gather from the lower
+//    triangle) with one arg-max candidate per workgroup; the second column pass decides by itself (every workgroup combines the first
+//    pass's candidates in the same fixed order) whether it has to run; a single-workgroup pivot kernel takes the final decision, swaps,
+//    scales, writes the L column(s), subdiag and the pivot record, updates the trailing diagonal and finds the next diagonal arg-max.
+//    Everything is predicated on device state: Partial / PartialDiag panels run without a host synchronisation, Rook / RookDiag read
+//    one flag back per rook iteration.  After the panel: one StrictTriangularLower MFMA product A_r -= W A_l^T, the LU row-interchange
+//    kernel on the columns left of the panel, and one read-back of the panel's length (63 or 64).
+//  * Ties of every arg-max go to the lowest index (strict >, rows in ascending order), as in the reference.
+#include "common.h"
+
+using namespace fh;
+
+namespace {
+
+constexpr int LB_NB = 64;   // panel width, most rows of the leaf
+constexpr int LB_LDP = 65;  // pitch of the leaf's LDS image (odd: rows and columns are both conflict free)
+constexpr int LB_NT = 256;  // threads of the leaf and of a column workgroup
+constexpr int LB_PT = 1024; // threads of the pivot workgroup
+constexpr int LB_NOIDX = 0x7fffffff;
+
+// device state of a factorization
+enum { ST_K = 0, ST_DONE, ST_I0, ST_I1, ST_NEED2, ST_NOTHING, ST_AGAIN, ST_N2X2, ST_COUNT = 16 };
+
+template <typename T> struct Cand {
+	T v;
+	int i;
+};
+
+template <typename T> static __device__ __forceinline__ T lb_alpha() { return ((T) 1 + sqrt((T) 17)) * (T) 0.125; }
+
+// larger value wins, equal values: the lower index
+template <typename T> static __device__ __forceinline__ void wave_argmax(T &v, int &i)
+{
+#pragma unroll
+	for (int off = 32; off >= 1; off >>= 1) {
+		const T ov = __shfl_xor(v, off, 64);
+		const int oi = __shfl_xor(i, off, 64);
+		if (ov > v || (ov == v && oi < i)) {
+			v = ov;
+			i = oi;
+		}
+	}
+}
+
+// workgroup arg-max of NT threads; every thread returns with the result.  s_v / s_i: NT / 64 entries.
+template <typename T, int NT> static __device__ __forceinline__ void block_argmax(T &v, int &i, T *s_v, int *s_i)
+{
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	wave_argmax(v, i);
+	__syncthreads(); // s_v / s_i may still be read from the previous use
+	if (lane == 0) {
+		s_v[wave] = v;
+		s_i[wave] = i;
+	}
+	__syncthreads();
+	v = s_v[0];
+	i = s_i[0];
+#pragma unroll
+	for (int w = 1; w < NT / 64; ++w) {
+		const T ov = s_v[w];
+		const int oi = s_i[w];
+		if (ov > v || (ov == v && oi < i)) {
+			v = ov;
+			i = oi;
+		}
+	}
+}
+
+// ------------------------------------------------------------------------------------------------ leaf
+template <typename T> static __device__ __forceinline__ void leaf_sym_swap(T *S, int m, int a, int b)
+{
+	const int tid = threadIdx.x;
+	if (tid < m) { // rows a, b over all columns
+		const T x = S[tid * LB_LDP + a];
+		S[tid * LB_LDP + a] = S[tid * LB_LDP + b];
+		S[tid * LB_LDP + b] = x;
+	}
+	__syncthreads();
+	if (tid < m) { // columns a, b over all rows
+		const T x = S[a * LB_LDP + tid];
+		S[a * LB_LDP + tid] = S[b * LB_LDP + tid];
+		S[b * LB_LDP + tid] = x;
+	}
+	__syncthreads();
+}
+
+// max |S[r][idx]| over r in [k, m), r != idx (column idx of the symmetric image); gamma < 0: no such row
+template <typename T> static __device__ __forceinline__ void leaf_offdiag(const T *S, int k, int m, int idx, T &gamma, int &r)
+{
+	const int lane = threadIdx.x & 63;
+	gamma = (lane >= k && lane < m && lane != idx) ? fabs(S[idx * LB_LDP + lane]) : (T) -1;
+	r = lane;
+	wave_argmax(gamma, r);
+}
+
+// A: the trailing m x m block (m <= 64); sub: its part of subdiag; piv: m pivot rows relative to the block; st: device state
+template <typename T>
+__global__ __launch_bounds__(LB_NT) void lblt_leaf_kernel(T *A, idx_t rs, idx_t cs, int m, T *sub, idx_t ss, int *piv, int *st, int rook,
+							   int diagonal)
+{
+	__shared__ T S[LB_NB * LB_LDP];
+	__shared__ T s_sub[LB_NB];
+	__shared__ int s_piv[LB_NB];
+	const int tid = threadIdx.x, lane = tid & 63;
+	const T alpha = lb_alpha<T>();
+	for (int e = tid; e < m * m; e += LB_NT) {
+		const int i = e % m, j = e / m;
+		S[j * LB_LDP + i] = j <= i ? A[(idx_t) i * rs + (idx_t) j * cs] : A[(idx_t) j * rs + (idx_t) i * cs];
+	}
+	int n2 = 0;
+	int k = 0;
+	while (k < m) {
+		__syncthreads();
+		// ---- decision: every wavefront computes the same one from the same image
+		int i0 = k, i1 = -1, npiv = 1;
+		if (diagonal) {
+			T v = (lane >= k && lane < m) ? fabs(S[lane * LB_LDP + lane]) : (T) -1;
+			i0 = lane;
+			wave_argmax(v, i0);
+		}
+		T gamma_i;
+		int r;
+		leaf_offdiag(S, k, m, i0, gamma_i, r);
+		bool nothing = false;
+		if (k + 1 == m || gamma_i == (T) 0) {
+			nothing = true;
+		} else if (fabs(S[i0 * LB_LDP + i0]) >= alpha * gamma_i) {
+			npiv = 1;
+		} else {
+			i1 = r;
+			if (rook) {
+				for (int it = 0;; ++it) { // (the cap only matters for non-finite input)
+					T gamma_r;
+					int s;
+					leaf_offdiag(S, k, m, i1, gamma_r, s);
+					if (fabs(S[i1 * LB_LDP + i1]) >= alpha * gamma_r) {
+						npiv = 1;
+						i0 = i1;
+						break;
+					} else if (s == i0 || gamma_i == gamma_r || it >= m) {
+						npiv = 2;
+						break;
+					} else {
+						i0 = i1;
+						i1 = s;
+						gamma_i = gamma_r;
+					}
+				}
+			} else {
+				T gamma_r;
+				int s;
+				leaf_offdiag(S, k, m, i1, gamma_r, s);
+				if (fabs(S[i0 * LB_LDP + i0]) >= (alpha * gamma_r) * (gamma_r / gamma_i)) {
+					npiv = 1;
+				} else if (fabs(S[i1 * LB_LDP + i1]) >= alpha * gamma_r) {
+					npiv = 1;
+					i0 = i1;
+				} else {
+					npiv = 2;
+				}
+			}
+		}
+		if (npiv == 2 && i0 > i1) {
+			const int t = i0;
+			i0 = i1;
+			i1 = t;
+		}
+		__syncthreads();
+		if (i0 != k)
+			leaf_sym_swap(S, m, k, i0);
+		if (npiv == 2 && i1 != k + 1)
+			leaf_sym_swap(S, m, k + 1, i1);
+		if (nothing) {
+			if (tid == 0) {
+				s_sub[k] = (T) 0;
+				s_piv[k] = i0;
+			}
+		} else if (npiv == 1) {
+			const T dinv = (T) 1 / S[k * LB_LDP + k];
+			const int mm = m - k - 1;
+			for (int e = tid; e < mm * mm; e += LB_NT) {
+				const int i = k + 1 + e % mm, j = k + 1 + e / mm;
+				if (i < j)
+					continue;
+				const T w = S[k * LB_LDP + j] * dinv;
+				const T v = fh_fma(S[k * LB_LDP + i], -w, S[j * LB_LDP + i]);
+				S[j * LB_LDP + i] = v;
+				S[i * LB_LDP + j] = v;
+			}
+			__syncthreads();
+			if (tid > k && tid < m)
+				S[k * LB_LDP + tid] *= dinv;
+			if (tid == 0) {
+				s_sub[k] = (T) 0;
+				s_piv[k] = i0;
+			}
+		} else {
+			const T a00 = S[k * LB_LDP + k], a11 = S[(k + 1) * LB_LDP + k + 1], a10 = S[k * LB_LDP + k + 1];
+			const T d10_inv = (T) 1 / fabs(a10);
+			const T d00 = a00 * d10_inv, d11 = a11 * d10_inv;
+			const T t = (T) 1 / (d00 * d11 - (T) 1);
+			const T d10 = a10 * d10_inv;
+			const T d = t * d10_inv;
+			const int mm = m - k - 2;
+			for (int e = tid; e < mm * mm; e += LB_NT) {
+				const int i = k + 2 + e % mm, j = k + 2 + e / mm;
+				if (i < j)
+					continue;
+				const T x0 = S[k * LB_LDP + j], x1 = S[(k + 1) * LB_LDP + j];
+				const T w0 = (x0 * d11 - x1 * d10) * d;
+				const T w1 = (x1 * d00 - x0 * d10) * d;
+				T v = S[j * LB_LDP + i];
+				v = fh_fma(S[k * LB_LDP + i], -w0, v);
+				v = fh_fma(S[(k + 1) * LB_LDP + i], -w1, v);
+				S[j * LB_LDP + i] = v;
+				S[i * LB_LDP + j] = v;
+			}
+			__syncthreads();
+			if (tid > k + 1 && tid < m) {
+				const T x0 = S[k * LB_LDP + tid], x1 = S[(k + 1) * LB_LDP + tid];
+				S[k * LB_LDP + tid] = (x0 * d11 - x1 * d10) * d;
+				S[(k + 1) * LB_LDP + tid] = (x1 * d00 - x0 * d10) * d;
+			}
+			if (tid == 0) {
+				S[k * LB_LDP + k + 1] = (T) 0;
+				s_sub[k] = a10;
+				s_sub[k + 1] = (T) 0;
+				s_piv[k] = i0;
+				s_piv[k + 1] = i1;
+			}
+			++n2;
+		}
+		k += npiv;
+	}
+	__syncthreads();
+	for (int e = tid; e < m * m; e += LB_NT) {
+		const int i = e % m, j = e / m;
+		if (j <= i)
+			A[(idx_t) i * rs + (idx_t) j * cs] = S[j * LB_LDP + i];
+	}
+	if (tid < m) {
+		sub[(idx_t) tid * ss] = s_sub[tid];
+		piv[tid] = s_piv[tid];
+	}
+	if (tid == 0)
+		st[ST_N2X2] += n2;
+}
+
+// ------------------------------------------------------------------------------------------------ panel
+// start of a panel on the m x m trailing block Ab: k = 0 and the first diagonal arg-max
+template <typename T> __global__ __launch_bounds__(LB_PT) void lblt_panel_init_kernel(const T *Ab, idx_t rs, idx_t cs, int m, int *st, int diagonal)
+{
+	__shared__ T s_v[LB_PT / 64];
+	__shared__ int s_i[LB_PT / 64];
+	const int tid = threadIdx.x;
+	int i0 = 0;
+	if (diagonal) {
+		T v = (T) -1;
+		i0 = LB_NOIDX;
+		for (int r = tid; r < m; r += LB_PT) {
+			const T x = fabs(Ab[(idx_t) r * (rs + cs)]);
+			if (x > v) {
+				v = x;
+				i0 = r;
+			}
+		}
+		block_argmax<T, LB_PT>(v, i0, s_v, s_i);
+		if (i0 == LB_NOIDX)
+			i0 = 0;
+	}
+	if (tid == 0) {
+		st[ST_K] = 0;
+		st[ST_DONE] = 0;
+		st[ST_I0] = i0;
+		st[ST_I1] = 0;
+		st[ST_NEED2] = 0;
+		st[ST_NOTHING] = 0;
+		st[ST_AGAIN] = 0;
+	}
+}
+
+// Candidate column of the lazily updated trailing matrix: W[:, k + which] = a(:, idx) - A_l W_l[idx, :]^T over the rows k .. m - 1, with
+// the current diagonal entry at row idx, and this workgroup's arg-max candidate of the off-diagonal part.  which == 0: idx = i0.
+// which == 1: idx = i1 -- with from_state == 0 every workgroup first takes the decision "is a second column needed" from the first pass's
+// candidates (workgroup 0 records it for the pivot kernel); with from_state == 1 (a further rook iteration) the state says so.
+template <typename T>
+__global__ __launch_bounds__(LB_NT) void lblt_col_kernel(const T *Ab, idx_t rs, idx_t cs, int m, T *W, int *st, T *fv, Cand<T> *cands, int nwg,
+							  int which, int from_state)
+{
+	__shared__ T s_v[LB_NT / 64];
+	__shared__ int s_i[LB_NT / 64];
+	__shared__ T s_w[LB_NB];
+	if (st[ST_DONE])
+		return;
+	const int tid = threadIdx.x;
+	const int k = st[ST_K];
+	int idx;
+	if (which == 0) {
+		idx = st[ST_I0];
+	} else if (from_state) {
+		if (!st[ST_AGAIN])
+			return;
+		idx = st[ST_I1];
+	} else {
+		const int i0 = st[ST_I0];
+		T g = (T) -1;
+		int r = LB_NOIDX;
+		for (int w = tid; w < nwg; w += LB_NT) { // (ascending w: ascending rows)
+			const Cand<T> c = cands[w];
+			if (c.v > g || (c.v == g && c.i < r)) {
+				g = c.v;
+				r = c.i;
+			}
+		}
+		block_argmax<T, LB_NT>(g, r, s_v, s_i);
+		const bool nothing = g == (T) 0 || r == LB_NOIDX; // (no index: non-finite input)
+		const bool need2 = !nothing && !(fabs(Ab[(idx_t) i0 * (rs + cs)]) >= lb_alpha<T>() * g);
+		if (blockIdx.x == 0 && tid == 0) {
+			st[ST_NEED2] = need2;
+			st[ST_NOTHING] = nothing;
+			st[ST_I1] = r;
+			fv[0] = g;
+		}
+		if (!need2)
+			return;
+		idx = r;
+	}
+	if (tid < k)
+		s_w[tid] = W[idx + (idx_t) tid * m];
+	__syncthreads();
+	const int r = blockIdx.x * LB_NT + tid;
+	T v = (T) -1;
+	int vi = LB_NOIDX;
+	if (r >= k && r < m) {
+		T acc;
+		if (r == idx) {
+			acc = Ab[(idx_t) idx * (rs + cs)];
+		} else {
+			acc = r < idx ? Ab[(idx_t) idx * rs + (idx_t) r * cs] : Ab[(idx_t) r * rs + (idx_t) idx * cs];
+			const T *al = Ab + (idx_t) r * rs;
+			for (int j = 0; j < k; ++j)
+				acc = fh_fma(-al[(idx_t) j * cs], s_w[j], acc);
+			v = fabs(acc);
+			vi = r;
+		}
+		W[r + (idx_t) (k + which) * m] = acc;
+	}
+	block_argmax<T, LB_NT>(v, vi, s_v, s_i);
+	if (tid == 0) {
+		Cand<T> c;
+		c.v = v;
+		c.i = vi;
+		cands[which * nwg + blockIdx.x] = c;
+	}
+}
+
+// swap of the indices a < b of the symmetric matrix stored in the lower triangle of Ab, restricted to the trailing part that starts at
+// column k (factor.rs:37-53), together with the rows a, b of the panel's L columns (0 .. k - 1) and of the first wc columns of W
+template <typename T>
+static __device__ __forceinline__ void panel_sym_swap(T *Ab, idx_t rs, idx_t cs, int m, T *W, int wc, int a, int b)
+{
+	const int tid = threadIdx.x;
+	for (int r = b + 1 + tid; r < m; r += LB_PT) { // columns a, b below row b
+		T *p = Ab + (idx_t) r * rs;
+		const T x = p[(idx_t) a * cs];
+		p[(idx_t) a * cs] = p[(idx_t) b * cs];
+		p[(idx_t) b * cs] = x;
+	}
+	for (int c = tid; c < a; c += LB_PT) { // rows a, b left of column a (the panel's L columns and the trailing columns before a)
+		T *p = Ab + (idx_t) c * cs;
+		const T x = p[(idx_t) a * rs];
+		p[(idx_t) a * rs] = p[(idx_t) b * rs];
+		p[(idx_t) b * rs] = x;
+	}
+	for (int t = a + 1 + tid; t < b; t += LB_PT) { // column a between the rows <-> row b between the columns
+		T *p = Ab + (idx_t) t * rs + (idx_t) a * cs, *q = Ab + (idx_t) b * rs + (idx_t) t * cs;
+		const T x = *p;
+		*p = *q;
+		*q = x;
+	}
+	for (int c = tid; c < wc; c += LB_PT) {
+		T *p = W + (idx_t) c * m;
+		const T x = p[a];
+		p[a] = p[b];
+		p[b] = x;
+	}
+	if (tid == 0) {
+		T *p = Ab + (idx_t) a * (rs + cs), *q = Ab + (idx_t) b * (rs + cs);
+		const T x = *p;
+		*p = *q;
+		*q = x;
+	}
+	__syncthreads();
+}
+
+// One workgroup: final decision of the step, swaps, elimination, pivot record, next diagonal arg-max (factor.rs:543-679).
+// sub: the panel's part of subdiag; piv: its pivot rows, relative to the block.
+template <typename T>
+__global__ __launch_bounds__(LB_PT) void lblt_pivot_kernel(T *Ab, idx_t rs, idx_t cs, int m, T *W, int *st, T *fv, const Cand<T> *cands, int nwg,
+							    T *sub, idx_t ss, int *piv, int rook, int diagonal)
+{
+	__shared__ T s_v[LB_PT / 64];
+	__shared__ int s_i[LB_PT / 64];
+	if (st[ST_DONE])
+		return;
+	const int tid = threadIdx.x;
+	const T alpha = lb_alpha<T>();
+	const int k = st[ST_K];
+	int i0 = st[ST_I0], i1 = st[ST_I1];
+	const bool nothing = st[ST_NOTHING] != 0, need2 = st[ST_NEED2] != 0;
+	const T gamma_i = fv[0];
+	int npiv = 1;
+	bool use1 = false; // the pivot column is the second candidate column
+	__syncthreads();   // every thread has read the state before thread 0 rewrites it
+	if (!nothing && need2) {
+		T gamma_r = (T) -1;
+		int s = LB_NOIDX;
+		for (int w = tid; w < nwg; w += LB_PT) {
+			const Cand<T> c = cands[nwg + w];
+			if (c.v > gamma_r || (c.v == gamma_r && c.i < s)) {
+				gamma_r = c.v;
+				s = c.i;
+			}
+		}
+		block_argmax<T, LB_PT>(gamma_r, s, s_v, s_i);
+		const T d0 = fabs(Ab[(idx_t) i0 * (rs + cs)]), d1 = fabs(Ab[(idx_t) i1 * (rs + cs)]);
+		if (!rook) {
+			if (d0 >= (alpha * gamma_r) * (gamma_r / gamma_i)) {
+				npiv = 1;
+			} else if (d1 >= alpha * gamma_r) {
+				npiv = 1;
+				i0 = i1;
+				use1 = true;
+			} else {
+				npiv = 2;
+			}
+		} else {
+			if (d1 >= alpha * gamma_r) {
+				npiv = 1;
+				i0 = i1;
+				use1 = true;
+			} else if (s == i0 || gamma_i == gamma_r || s == LB_NOIDX) {
+				npiv = 2;
+			} else { // one more rook iteration: (i0, i1, gamma_i) <- (i1, s, gamma_r), the second column becomes the first
+				for (int r = k + tid; r < m; r += LB_PT)
+					W[r + (idx_t) k * m] = W[r + (idx_t) (k + 1) * m];
+				if (tid == 0) {
+					st[ST_I0] = i1;
+					st[ST_I1] = s;
+					fv[0] = gamma_r;
+					st[ST_AGAIN] = 1;
+				}
+				return;
+			}
+		}
+	}
+	if (use1) {
+		for (int r = k + tid; r < m; r += LB_PT)
+			W[r + (idx_t) k * m] = W[r + (idx_t) (k + 1) * m];
+	}
+	if (npiv == 2 && i0 > i1) {
+		for (int r = k + tid; r < m; r += LB_PT) {
+			const T x = W[r + (idx_t) k * m];
+			W[r + (idx_t) k * m] = W[r + (idx_t) (k + 1) * m];
+			W[r + (idx_t) (k + 1) * m] = x;
+		}
+		const int t = i0;
+		i0 = i1;
+		i1 = t;
+	}
+	__syncthreads();
+	if (i0 != k)
+		panel_sym_swap(Ab, rs, cs, m, W, k + npiv, k, i0);
+	if (npiv == 2 && i1 != k + 1)
+		panel_sym_swap(Ab, rs, cs, m, W, k + npiv, k + 1, i1);
+	const T *w0p = W + (idx_t) k * m, *w1p = W + (idx_t) (k + 1) * m;
+	if (nothing) {
+		// the updated column is zero below the diagonal: that is the L column (the stored one is not up to date)
+		for (int r = k + 1 + tid; r < m; r += LB_PT)
+			Ab[(idx_t) r * rs + (idx_t) k * cs] = w0p[r];
+		if (tid == 0)
+			sub[(idx_t) k * ss] = (T) 0;
+	} else if (npiv == 1) {
+		const T diag = w0p[k];
+		const T dinv = (T) 1 / diag;
+		for (int r = k + 1 + tid; r < m; r += LB_PT) {
+			const T l = w0p[r] * dinv;
+			Ab[(idx_t) r * rs + (idx_t) k * cs] = l;
+			T *dd = Ab + (idx_t) r * (rs + cs);
+			*dd = *dd - diag * (l * l);
+		}
+		if (tid == 0)
+			sub[(idx_t) k * ss] = (T) 0;
+	} else {
+		const T a00 = w0p[k], a11 = w1p[k + 1], a10 = w0p[k + 1];
+		const T d10_inv = (T) 1 / fabs(a10);
+		const T d00 = a00 * d10_inv, d11 = a11 * d10_inv;
+		const T t = (T) 1 / (d00 * d11 - (T) 1);
+		const T d10 = a10 * d10_inv;
+		const T d = t * d10_inv;
+		__syncthreads(); // a10 is read by every thread before thread 0 clears it
+		for (int r = k + 2 + tid; r < m; r += LB_PT) {
+			const T x0 = w0p[r], x1 = w1p[r];
+			const T w0 = (x0 * d11 - x1 * d10) * d;
+			const T w1 = (x1 * d00 - x0 * d10) * d;
+			T *dd = Ab + (idx_t) r * (rs + cs);
+			*dd = *dd - x0 * w0 - x1 * w1;
+			Ab[(idx_t) r * rs + (idx_t) k * cs] = w0;
+			Ab[(idx_t) r * rs + (idx_t) (k + 1) * cs] = w1;
+		}
+		if (tid == 0) {
+			sub[(idx_t) k * ss] = a10;
+			sub[(idx_t) (k + 1) * ss] = (T) 0;
+			W[(k + 1) + (idx_t) k * m] = (T) 0;
+			Ab[(idx_t) (k + 1) * rs + (idx_t) k * cs] = (T) 0;
+		}
+	}
+	const int knew = k + npiv;
+	__syncthreads();
+	int inext = knew;
+	if (diagonal) {
+		T v = (T) -1;
+		inext = LB_NOIDX;
+		for (int r = knew + tid; r < m; r += LB_PT) {
+			const T x = fabs(Ab[(idx_t) r * (rs + cs)]);
+			if (x > v) {
+				v = x;
+				inext = r;
+			}
+		}
+		block_argmax<T, LB_PT>(v, inext, s_v, s_i);
+		if (inext == LB_NOIDX)
+			inext = knew;
+	}
+	if (tid == 0) {
+		piv[k] = i0;
+		if (npiv == 2) {
+			piv[k + 1] = i1;
+			st[ST_N2X2] += 1;
+		}
+		st[ST_K] = knew;
+		st[ST_DONE] = knew >= LB_NB - 1;
+		st[ST_I0] = inext;
+		st[ST_NEED2] = 0;
+		st[ST_NOTHING] = 0;
+		st[ST_AGAIN] = 0;
+	}
+}
+
+thread_local size_t g_last[4] = {0, 0, 0, 0}; // panels, leaf rows, 2 x 2 pivots, host synchronisations inside panels
+
+// reads `cnt` ints of the device state back (one host synchronisation)
+void read_state(const int *st, int *out, int first, int cnt)
+{
+	int *h = ctx().pinned_ints();
+	FH_HIP(hipMemcpyAsync(h, st + first, (size_t) cnt * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+	ctx().sync();
+	for (int i = 0; i < cnt; ++i)
+		out[i] = h[i];
+}
+
+// A: n x n device view, sub: device, stride ss.  perm / perm_inv: host, n entries.  Returns the transposition count.
+template <typename T> long lblt_dev(MatV<T> A, T *sub, idx_t ss, idx_t *perm, idx_t *perm_inv, bool rook, bool diagonal)
+{
+	const idx_t n = A.nrows;
+	g_last[0] = g_last[1] = g_last[2] = g_last[3] = 0;
+	if (n == 0)
+		return 0;
+	FH_CHECK(n < ((idx_t) 1 << 30), "lblt: dimension too large");
+	hipStream_t s = ctx().stream;
+	const int nwg_max = (int) ((n + LB_NT - 1) / LB_NT);
+	Scratch stb(ST_COUNT * sizeof(int)), fvb(4 * sizeof(T)), pivb((size_t) n * sizeof(int)), cab((size_t) 2 * nwg_max * sizeof(Cand<T>));
+	Scratch wb(n > LB_NB ? (size_t) n * LB_NB * sizeof(T) : 256);
+	int *st = stb.as<int>(), *piv = pivb.as<int>();
+	T *fv = fvb.as<T>(), *W = wb.as<T>();
+	Cand<T> *cands = cab.as<Cand<T>>();
+	FH_HIP(hipMemsetAsync(st, 0, ST_COUNT * sizeof(int), s));
+	std::vector<idx_t> starts; // block starts: the pivot records are relative to them
+	idx_t k0 = 0;
+	while (n - k0 > LB_NB) {
+		const int m = (int) (n - k0);
+		const int nwg = (m + LB_NT - 1) / LB_NT;
+		T *Ab = A.p + k0 * (A.rs + A.cs);
+		T *subp = sub + k0 * ss;
+		int *pv = piv + k0;
+		hipLaunchKernelGGL(lblt_panel_init_kernel<T>, dim3(1), dim3(LB_PT), 0, s, Ab, A.rs, A.cs, m, st, (int) diagonal);
+		for (int step = 0; step < LB_NB - 1; ++step) {
+			hipLaunchKernelGGL(lblt_col_kernel<T>, dim3(nwg), dim3(LB_NT), 0, s, Ab, A.rs, A.cs, m, W, st, fv, cands, nwg, 0, 0);
+			hipLaunchKernelGGL(lblt_col_kernel<T>, dim3(nwg), dim3(LB_NT), 0, s, Ab, A.rs, A.cs, m, W, st, fv, cands, nwg, 1, 0);
+			hipLaunchKernelGGL(lblt_pivot_kernel<T>, dim3(1), dim3(LB_PT), 0, s, Ab, A.rs, A.cs, m, W, st, fv, cands, nwg, subp, ss, pv,
+					   (int) rook, (int) diagonal);
+			if (rook) { // the length of the rook loop depends on the data: one flag per iteration
+				int h[2];
+				for (int it = 0;; ++it) {
+					read_state(st, h, ST_AGAIN, 1);
+					++g_last[3];
+					if (!h[0])
+						break;
+					FH_CHECK(it < m, "lblt: the rook search did not terminate (non-finite input?)");
+					hipLaunchKernelGGL(lblt_col_kernel<T>, dim3(nwg), dim3(LB_NT), 0, s, Ab, A.rs, A.cs, m, W, st, fv, cands, nwg, 1, 1);
+					hipLaunchKernelGGL(lblt_pivot_kernel<T>, dim3(1), dim3(LB_PT), 0, s, Ab, A.rs, A.cs, m, W, st, fv, cands, nwg, subp,
+							   ss, pv, (int) rook, (int) diagonal);
+				}
+			}
+		}
+		FH_HIP(hipGetLastError());
+		int ke;
+		read_state(st, &ke, ST_K, 1); // 63 or 64
+		FH_CHECK(ke == LB_NB - 1 || ke == LB_NB, "lblt: panel ended at an unexpected column");
+		const idx_t mr = m - ke;
+		MatV<T> Ablk{Ab, m, m, A.rs, A.cs};
+		MatV<T> Wv{W, m, LB_NB, 1, m};
+		// A_r(strict lower) -= W A_l^T (factor.rs:684-694); the diagonal is already up to date
+		matmul_triangular_dev<T>(Ablk.sub(ke, ke, mr, mr), (int) FaerBlock_StrictTriangularLower, true, Wv.sub(ke, 0, mr, ke).c(),
+					 (int) FaerBlock_Rectangular, Ablk.sub(ke, 0, mr, ke).t().c(), (int) FaerBlock_Rectangular, (T) -1);
+		if (k0 > 0)
+			laswp_rows_dev<T>(A.sub(k0, 0, m, k0), pv, ke); // factor.rs:748-779
+		starts.push_back(k0);
+		k0 += ke;
+		++g_last[0];
+	}
+	{
+		const int m = (int) (n - k0);
+		hipLaunchKernelGGL(lblt_leaf_kernel<T>, dim3(1), dim3(LB_NT), 0, s, A.p + k0 * (A.rs + A.cs), A.rs, A.cs, m, sub + k0 * ss, ss, piv + k0,
+				   st, (int) rook, (int) diagonal);
+		FH_HIP(hipGetLastError());
+		if (k0 > 0)
+			laswp_rows_dev<T>(A.sub(k0, 0, m, k0), piv + k0, m);
+		starts.push_back(k0);
+		g_last[1] = (size_t) m;
+	}
+	std::vector<int> hp((size_t) n);
+	int n2;
+	FH_HIP(hipMemcpyAsync(hp.data(), piv, (size_t) n * sizeof(int), hipMemcpyDeviceToHost, s));
+	read_state(st, &n2, ST_N2X2, 1);
+	g_last[2] = (size_t) n2;
+	// factor.rs:1214-1227
+	for (idx_t i = 0; i < n; ++i)
+		perm[i] = i;
+	long count = 0;
+	size_t b = 0;
+	for (idx_t i = 0; i < n; ++i) {
+		while (b + 1 < starts.size() && starts[b + 1] <= i)
+			++b;
+		const idx_t p = starts[b] + hp[(size_t) i];
+		FH_CHECK(p >= i && p < n, "lblt: pivot record out of range");
+		if (p != i)
+			++count;
+		std::swap(perm[i], perm[p]);
+	}
+	for (idx_t i = 0; i < n; ++i)
+		perm_inv[perm[i]] = i;
+	return count;
+}
+
+// ------------------------------------------------------------------------------------------------ solve / reconstruct
+// x <- B^-1 x for the block diagonal B (solve.rs:63-96): one thread per (block, right-hand side)
+template <typename T>
+__global__ void lblt_block_diag_solve_kernel(T *X, idx_t rs, idx_t cs, idx_t n, idx_t k, const T *d, idx_t ds, const T *sub, idx_t ss)
+{
+	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+	if (i >= n || j >= k)
+		return;
+	if (i > 0 && sub[(i - 1) * ss] != (T) 0)
+		return; // second row of a 2 x 2 block
+	T *x = X + i * rs + j * cs;
+	const T s = sub[i * ss];
+	if (s == (T) 0 || i + 1 >= n) {
+		*x = *x * ((T) 1 / d[i * ds]);
+	} else {
+		const T akp1k = (T) 1 / s;
+		const T ak = akp1k * d[i * ds], akp1 = akp1k * d[(i + 1) * ds];
+		const T denom = (T) 1 / (ak * akp1 - (T) 1);
+		const T xk = x[0] * akp1k, xkp1 = x[rs] * akp1k;
+		x[0] = (akp1 * xk - xkp1) * denom;
+		x[rs] = (ak * xkp1 - xk) * denom;
+	}
+}
+
+// X <- L_unit B, n x n column major (reconstruct.rs:35-60)
+template <typename T>
+__global__ void lblt_scale_kernel(T *X, idx_t n, const T *L, idx_t rs, idx_t cs, const T *d, idx_t ds, const T *sub, idx_t ss)
+{
+	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+	if (i >= n || j >= n)
+		return;
+	auto lu = [&](idx_t r, idx_t c) -> T { return r > c ? L[r * rs + c * cs] : (r == c ? (T) 1 : (T) 0); };
+	T v = lu(i, j) * d[j * ds];
+	const T s = sub[j * ss];
+	if (s != (T) 0 && j + 1 < n)
+		v += lu(i, j + 1) * s;
+	else if (j > 0 && sub[(j - 1) * ss] != (T) 0)
+		v += lu(i, j - 1) * sub[(j - 1) * ss];
+	X[i + j * n] = v;
+}
+
+// lower(out)[i, j] = tmp[max(p_i, p_j), min(p_i, p_j)], p = perm_inv (reconstruct.rs:72-83); tmp n x n column major
+template <typename T> __global__ void lblt_sym_gather_kernel(T *out, idx_t rs, idx_t cs, idx_t n, const T *tmp, const idx_t *pinv)
+{
+	const idx_t i = (idx_t) blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+	if (i >= n || j > i)
+		return;
+	const idx_t pi = pinv[i], pj = pinv[j];
+	out[i * rs + j * cs] = pi >= pj ? tmp[pi + pj * n] : tmp[pj + pi * n];
+}
+
+template <typename T> MatV<const T> view(FaerMatRef m)
+{
+	return MatV<const T>{static_cast<const T *>(m.ptr), (idx_t) m.nrows, (idx_t) m.ncols, (idx_t) m.row_stride, (idx_t) m.col_stride};
+}
+template <typename T> MatV<T> view(FaerMatMut m)
+{
+	return MatV<T>{static_cast<T *>(m.ptr), (idx_t) m.nrows, (idx_t) m.ncols, (idx_t) m.row_stride, (idx_t) m.col_stride};
+}
+template <typename T> MatV<const T> vview(FaerVecRef v) { return MatV<const T>{static_cast<const T *>(v.ptr), (idx_t) v.len, 1, (idx_t) v.stride, 0}; }
+template <typename T> MatV<T> vview(FaerVecMut v) { return MatV<T>{static_cast<T *>(v.ptr), (idx_t) v.len, 1, (idx_t) v.stride, 0}; }
+
+template <typename I> void upload_perm(Scratch &buf, const void *perm_host, idx_t n)
+{
+	std::vector<idx_t> p64((size_t) n);
+	for (idx_t i = 0; i < n; ++i) {
+		p64[(size_t) i] = (idx_t) static_cast<const I *>(perm_host)[i];
+		FH_CHECK(p64[(size_t) i] >= 0 && p64[(size_t) i] < n, "permutation index out of range");
+	}
+	FH_HIP(hipMemcpyAsync(buf.p, p64.data(), (size_t) n * sizeof(idx_t), hipMemcpyHostToDevice, ctx().stream));
+	ctx().sync(); // p64 goes out of scope
+}
+
+// X[i, :] <- X[perm[i], :]
+template <typename T, typename I> void permute_rows(MatV<T> X, const void *perm_host)
+{
+	const idx_t n = X.nrows, k = X.ncols;
+	Scratch pb((size_t) n * sizeof(idx_t)), tb((size_t) n * (size_t) k * sizeof(T));
+	upload_perm<I>(pb, perm_host, n);
+	MatV<T> tmp{tb.as<T>(), n, k, 1, n};
+	gather_rows_dev<T>(tmp, X.c(), pb.as<idx_t>());
+	copy_dev<T>(X, tmp.c());
+	ctx().sync();
+}
+
+const char *strategy_name(int p)
+{
+	switch (p) {
+	case FaerPivotingStrategy_Partial: return "Partial";
+	case FaerPivotingStrategy_PartialDiag: return "PartialDiag";
+	case FaerPivotingStrategy_Rook: return "Rook";
+	case FaerPivotingStrategy_RookDiag: return "RookDiag";
+	case FaerPivotingStrategy_Full: return "Full";
+	}
+	return "?";
+}
+
+template <typename T, typename I>
+FaerLbltStatus factor_api(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut pf, FaerSliceMut pb, FaerLbltParams params)
+{
+	const idx_t n = (idx_t) A.nrows;
+	FH_CHECK(A.nrows == A.ncols, "lblt: matrix must be square");
+	FH_CHECK((idx_t) subdiag.len == n, "lblt: subdiag must have dim entries");
+	FH_CHECK((idx_t) pf.len == n && (idx_t) pb.len == n, "lblt: perm slices must have dim entries");
+	FH_CHECK(n == 0 || (!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr)), "lblt: perm slices must be host memory");
+	const int p = (int) params.pivoting;
+	if (p < (int) FaerPivotingStrategy_Partial || p >= (int) FaerPivotingStrategy_Full) {
+		fprintf(stderr, "faer_hip: fatal: lblt_factor_in_place: pivoting strategy %s (%d) is not implemented (Partial, PartialDiag, Rook, RookDiag only)\n",
+			strategy_name(p), p);
+		fflush(stderr);
+		abort();
+	}
+	const bool rook = p == FaerPivotingStrategy_Rook || p == FaerPivotingStrategy_RookDiag;
+	const bool diagonal = p == FaerPivotingStrategy_PartialDiag || p == FaerPivotingStrategy_RookDiag;
+	std::vector<idx_t> perm((size_t) n), perm_inv((size_t) n);
+	long nt;
+	{
+		Staged<T> a(view<T>(A), true, true);
+		Staged<T> sd(vview<T>(subdiag), false, true);
+		nt = lblt_dev<T>(a.dev, sd.dev.p, sd.dev.rs, perm.data(), perm_inv.data(), rook, diagonal);
+	}
+	I *f = static_cast<I *>(pf.ptr), *b = static_cast<I *>(pb.ptr);
+	for (idx_t i = 0; i < n; ++i) {
+		f[i] = (I) perm[(size_t) i];
+		b[i] = (I) perm_inv[(size_t) i];
+	}
+	FaerLbltStatus stt;
+	memset(&stt, 0, sizeof(stt));
+	stt.tag = FaerLbltStatus_Ok;
+	stt.ok.transposition_count = (size_t) nt;
+	return stt;
+}
+
+// solve.rs:35-104
+template <typename T, typename I>
+void solve_dev(MatV<const T> L, MatV<const T> d, MatV<const T> sd, const void *pf, const void *pb, MatV<T> X)
+{
+	const idx_t n = L.nrows, k = X.ncols;
+	if (n == 0 || k == 0)
+		return;
+	permute_rows<T, I>(X, pf);
+	trsm_lower_dev<T>(L, true, X);
+	hipLaunchKernelGGL(lblt_block_diag_solve_kernel<T>, dim3((unsigned) ((n + 255) / 256), (unsigned) k), dim3(256), 0, ctx().stream, X.p, X.rs,
+			   X.cs, n, k, d.p, d.rs, sd.p, sd.rs);
+	FH_HIP(hipGetLastError());
+	trsm_upper_dev<T>(L.t(), true, X);
+	permute_rows<T, I>(X, pb);
+}
+
+template <typename T, typename I>
+void solve_api(FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs)
+{
+	const size_t n = L.nrows;
+	FH_CHECK(L.ncols == n && rhs.nrows == n && diag.len == n && subdiag.len == n && pf.len >= n && pb.len >= n, "lblt solve: dimension mismatch");
+	FH_CHECK(rhs.ncols < 65536, "lblt solve: too many right-hand sides");
+	FH_CHECK(n == 0 || (!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr)), "lblt solve: perm slices must be host memory");
+	Staged<const T> l(view<T>(L), true, false), d(vview<T>(diag), true, false), sd(vview<T>(subdiag), true, false);
+	Staged<T> x(view<T>(rhs), true, true);
+	solve_dev<T, I>(l.dev, d.dev, sd.dev, pf.ptr, pb.ptr, x.dev);
+}
+
+// reconstruct.rs:12-87 (the lower triangle of out only)
+template <typename T, typename I>
+void reconstruct_api(FaerMatMut Out, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef pf, FaerSliceRef pb)
+{
+	const idx_t n = (idx_t) L.nrows;
+	FH_CHECK((idx_t) L.ncols == n && (idx_t) Out.nrows == n && (idx_t) Out.ncols == n && (idx_t) diag.len == n && (idx_t) subdiag.len == n &&
+			 (idx_t) pf.len >= n && (idx_t) pb.len >= n,
+		 "lblt reconstruct: dimension mismatch");
+	FH_CHECK(n < 65536, "lblt reconstruct: dimension too large");
+	if (n == 0)
+		return;
+	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "lblt reconstruct: perm slices must be host memory");
+	Staged<const T> l(view<T>(L), true, false), d(vview<T>(diag), true, false), sd(vview<T>(subdiag), true, false);
+	Staged<T> o(view<T>(Out), true, true); // the strict upper triangle is kept
+	Scratch xb((size_t) n * (size_t) n * sizeof(T) + 256), tb((size_t) n * (size_t) n * sizeof(T) + 256), pbuf((size_t) n * sizeof(idx_t));
+	MatV<T> X{xb.as<T>(), n, n, 1, n}, tmp{tb.as<T>(), n, n, 1, n};
+	const dim3 grid((unsigned) ((n + 255) / 256), (unsigned) n);
+	hipLaunchKernelGGL(lblt_scale_kernel<T>, grid, dim3(256), 0, ctx().stream, X.p, n, l.dev.p, l.dev.rs, l.dev.cs, d.dev.p, d.dev.rs, sd.dev.p,
+			   sd.dev.rs);
+	FH_HIP(hipGetLastError());
+	matmul_triangular_dev<T>(tmp, (int) FaerBlock_TriangularLower, false, l.dev, (int) FaerBlock_UnitTriangularLower, X.t().c(),
+				 (int) FaerBlock_Rectangular, (T) 1);
+	upload_perm<I>(pbuf, pb.ptr, n);
+	hipLaunchKernelGGL(lblt_sym_gather_kernel<T>, grid, dim3(256), 0, ctx().stream, o.dev.p, o.dev.rs, o.dev.cs, n, tmp.p, pbuf.as<idx_t>());
+	FH_HIP(hipGetLastError());
+	ctx().sync();
+}
+
+// inverse.rs:11-42: solve with the identity
+template <typename T, typename I>
+void inverse_api(FaerMatMut Out, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef pf, FaerSliceRef pb)
+{
+	const size_t n = L.nrows;
+	FH_CHECK(L.ncols == n && Out.nrows == n && Out.ncols == n && diag.len == n && subdiag.len == n && pf.len >= n && pb.len >= n,
+		 "lblt inverse: dimension mismatch");
+	FH_CHECK(n < 65536, "lblt inverse: dimension too large");
+	if (n == 0)
+		return;
+	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "lblt inverse: perm slices must be host memory");
+	Staged<const T> l(view<T>(L), true, false), d(vview<T>(diag), true, false), sd(vview<T>(subdiag), true, false);
+	Staged<T> o(view<T>(Out), false, true);
+	svd_identity_dev<T>(o.dev);
+	solve_dev<T, I>(l.dev, d.dev, sd.dev, pf.ptr, pb.ptr, o.dev);
+}
+
+FaerLayout lay(size_t bytes) { return FaerLayout{bytes, 64}; }
+size_t up64(size_t b) { return (b + 63) / 64 * 64; }
+
+} // namespace
+
+extern "C" {
+
+void faer_hip_debug_lblt_last(size_t out[4])
+{
+	for (int i = 0; i < 4; ++i)
+		out[i] = g_last[i];
+}
+
+#define X(suf, T)                                                                                                                                  \
+	FaerLbltParams libfaer_v0_23_LbltParams_##suf(void) { return FaerLbltParams{FaerPivotingStrategy_PartialDiag, 128 * 128, 64}; }
+X(f64, double)
+X(f32, float)
+#undef X
+
+#define X(it, I, suf, T)                                                                                                                           \
+	FaerLayout libfaer_v0_23_lblt_factor_in_place_scratch_##it##_##suf(size_t dim, FaerPar par, FaerLbltParams params)                         \
+	{                                                                                                                                          \
+		(void) par;                                                                                                                        \
+		size_t bs = params.block_size; /* factor.rs:1128-1140 */                                                                           \
+		if (bs < 2 || dim <= bs)                                                                                                           \
+			bs = 0;                                                                                                                    \
+		return lay(dim == 0 ? 0 : up64(dim * sizeof(size_t)) + dim * bs * sizeof(T));                                                     \
+	}                                                                                                                                          \
+	FaerLbltStatus libfaer_v0_23_lblt_factor_in_place_##it##_##suf(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut perm_fwd,                    \
+								       FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerLbltParams params) \
+	{                                                                                                                                          \
+		(void) par;                                                                                                                        \
+		(void) mem;                                                                                                                        \
+		return factor_api<T, I>(A, subdiag, perm_fwd, perm_bwd, params);                                                                   \
+	}                                                                                                                                          \
+	FaerLayout libfaer_v0_23_lblt_solve_in_place_scratch_##it##_##suf(size_t dim, size_t rhs_ncols, FaerPar par)                               \
+	{                                                                                                                                          \
+		(void) par;                                                                                                                        \
+		return lay(dim * rhs_ncols * sizeof(T)); /* solve.rs:11-18 */                                                                      \
+	}                                                                                                                                          \
+	void libfaer_v0_23_lblt_solve_in_place_##it##_##suf(FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerConj A_conj,                    \
+							    FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par,             \
+							    FaerMemAlloc mem)                                                                      \
+	{                                                                                                                                          \
+		(void) A_conj;                                                                                                                     \
+		(void) par;                                                                                                                        \
+		(void) mem;                                                                                                                        \
+		solve_api<T, I>(L, diag, subdiag, perm_fwd, perm_bwd, rhs);                                                                        \
+	}                                                                                                                                          \
+	FaerLayout libfaer_v0_23_lblt_reconstruct_scratch_##it##_##suf(size_t dim, FaerPar par)                                                    \
+	{                                                                                                                                          \
+		(void) par;                                                                                                                        \
+		return lay(dim * dim * sizeof(T)); /* reconstruct.rs:4-10 */                                                                       \
+	}                                                                                                                                          \
+	void libfaer_v0_23_lblt_reconstruct_##it##_##suf(FaerMatMut A, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd,   \
+							 FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem)                                     \
+	{                                                                                                                                          \
+		(void) par;                                                                                                                        \
+		(void) mem;                                                                                                                        \
+		reconstruct_api<T, I>(A, L, diag, subdiag, perm_fwd, perm_bwd);                                                                    \
+	}                                                                                                                                          \
+	FaerLayout libfaer_v0_23_lblt_inverse_scratch_##it##_##suf(size_t dim, FaerPar par)                                                        \
+	{                                                                                                                                          \
+		(void) par;                                                                                                                        \
+		return lay(dim * dim * sizeof(T)); /* inverse.rs:3-9 */                                                                            \
+	}                                                                                                                                          \
+	void libfaer_v0_23_lblt_inverse_##it##_##suf(FaerMatMut A_inv, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd,   \
+						     FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem)                                         \
+	{                                                                                                                                          \
+		(void) par;                                                                                                                        \
+		(void) mem;                                                                                                                        \
+		inverse_api<T, I>(A_inv, L, diag, subdiag, perm_fwd, perm_bwd);                                                                    \
+	}
+X(u32, uint32_t, f64, double)
+X(u64, uint64_t, f64, double)
+X(u32, uint32_t, f32, float)
+X(u64, uint64_t, f32, float)
+#undef X
+
+} // extern "C"

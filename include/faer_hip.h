@@ -143,6 +143,20 @@ typedef struct FaerSvdStatus {
 		struct { size_t padding; } no_convergence;
 	};
 } FaerSvdStatus;
+/* LBLT (Bunch-Kaufman): faer.h:32-55, :156-160, :324-338, lib.rs:509-548, :576, :665 (cholesky/bunch_kaufman/factor.rs:8-36) */
+typedef enum FaerPivotingStrategy {
+	FaerPivotingStrategy_Partial = 0,
+	FaerPivotingStrategy_PartialDiag = 1,
+	FaerPivotingStrategy_Rook = 2,
+	FaerPivotingStrategy_RookDiag = 3,
+	FaerPivotingStrategy_Full = 4
+} FaerPivotingStrategy;
+typedef struct FaerLbltParams { FaerPivotingStrategy pivoting; size_t par_threshold; size_t block_size; } FaerLbltParams;
+typedef enum FaerLbltStatus_Tag { FaerLbltStatus_Ok = 0, FaerLbltStatus_Unknown = 1 } FaerLbltStatus_Tag;
+typedef struct FaerLbltStatus {
+	FaerLbltStatus_Tag tag;
+	union { struct { size_t transposition_count; } ok; };
+} FaerLbltStatus;
 /* faer-ffi/src/lib.rs:796-801; pointers to a real scalar of the matrix dtype (HOST memory), NULL == 0 */
 typedef struct FaerLltRegularization { const void *dynamic_regularization_delta; const void *dynamic_regularization_epsilon; } FaerLltRegularization;
 /* lib.rs:820-828: signs is a slice of i8 (HOST memory, `dim` entries) or a null ptr */
@@ -507,6 +521,57 @@ FAER_HIP_API FaerLayout libfaer_v0_23_svd_scratch_f64(size_t nrows, size_t ncols
 FAER_HIP_API FaerLayout libfaer_v0_23_svd_scratch_f32(size_t nrows, size_t ncols, FaerComputeSvdVectors compute_U, FaerComputeSvdVectors compute_V, FaerPar par, FaerSvdParams params);
 FAER_HIP_API FaerSvdStatus libfaer_v0_23_svd_f64(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerMatMut V, FaerPar par, FaerMemAlloc mem, FaerSvdParams params);
 FAER_HIP_API FaerSvdStatus libfaer_v0_23_svd_f32(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerMatMut V, FaerPar par, FaerMemAlloc mem, FaerSvdParams params);
+/* ---------------------------------------------------------------------------------------------
+ * 2g. LBLT: Bunch-Kaufman factorization of a symmetric indefinite matrix (faer-ffi/src/lib.rs:1288-1421;
+ *     cholesky/bunch_kaufman/factor.rs, solve.rs, reconstruct.rs, inverse.rs): P A P^T = L B L^T, B block diagonal with
+ *     1 x 1 and 2 x 2 blocks.  Only the LOWER triangle of A is read or written; the strict upper triangle is never touched.
+ *     On return the strict lower triangle holds the unit lower L, the diagonal holds the diagonal of B, subdiag[j] =
+ *     B[j+1, j] for a 2 x 2 block starting at j (then subdiag[j+1] == 0 and A[j+1, j] is stored as 0) and 0 for a 1 x 1
+ *     block.  perm_fwd[i] = source index of row i of P A P^T, perm_bwd its inverse (HOST memory, dim entries);
+ *     transposition_count = number of positions whose pivot index differs from the position.  Pivoting strategies
+ *     Partial, PartialDiag (the default), Rook and RookDiag follow the reference's decision tree, ties of every arg-max
+ *     going to the lowest index.  Full is a different level-2 algorithm and is NOT implemented: it aborts with a message
+ *     naming the strategy (the boundary's convention for unsupported input).  params.block_size and par_threshold are
+ *     hints and ignored: the GPU factors panels of 64 columns by the lazily updated W-panel algorithm and the last <= 64
+ *     rows in one LDS-resident workgroup (csrc/lblt.hip); the pivot sequence does not depend on the blocking in exact
+ *     arithmetic.  solve / reconstruct / inverse take L and the strided `diag` and `subdiag` vectors as the factorization
+ *     leaves them; reconstruct writes the lower triangle of A only, inverse the whole of A_inv.  Host or device operands,
+ *     any strides; par, mem and A_conj are accepted and ignored.  The scratch queries need no device.
+ * --------------------------------------------------------------------------------------------- */
+FAER_HIP_API FaerLbltParams libfaer_v0_23_LbltParams_f64(void);
+FAER_HIP_API FaerLbltParams libfaer_v0_23_LbltParams_f32(void);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_factor_in_place_scratch_u32_f64(size_t dim, FaerPar par, FaerLbltParams params);
+FAER_HIP_API FaerLbltStatus libfaer_v0_23_lblt_factor_in_place_u32_f64(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerLbltParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_solve_in_place_scratch_u32_f64(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_solve_in_place_u32_f64(FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_reconstruct_scratch_u32_f64(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_reconstruct_u32_f64(FaerMatMut A, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_inverse_scratch_u32_f64(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_inverse_u32_f64(FaerMatMut A_inv, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_factor_in_place_scratch_u32_f32(size_t dim, FaerPar par, FaerLbltParams params);
+FAER_HIP_API FaerLbltStatus libfaer_v0_23_lblt_factor_in_place_u32_f32(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerLbltParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_solve_in_place_scratch_u32_f32(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_solve_in_place_u32_f32(FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_reconstruct_scratch_u32_f32(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_reconstruct_u32_f32(FaerMatMut A, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_inverse_scratch_u32_f32(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_inverse_u32_f32(FaerMatMut A_inv, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_factor_in_place_scratch_u64_f64(size_t dim, FaerPar par, FaerLbltParams params);
+FAER_HIP_API FaerLbltStatus libfaer_v0_23_lblt_factor_in_place_u64_f64(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerLbltParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_solve_in_place_scratch_u64_f64(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_solve_in_place_u64_f64(FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_reconstruct_scratch_u64_f64(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_reconstruct_u64_f64(FaerMatMut A, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_inverse_scratch_u64_f64(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_inverse_u64_f64(FaerMatMut A_inv, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_factor_in_place_scratch_u64_f32(size_t dim, FaerPar par, FaerLbltParams params);
+FAER_HIP_API FaerLbltStatus libfaer_v0_23_lblt_factor_in_place_u64_f32(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerLbltParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_solve_in_place_scratch_u64_f32(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_solve_in_place_u64_f32(FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_reconstruct_scratch_u64_f32(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_reconstruct_u64_f32(FaerMatMut A, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_lblt_inverse_scratch_u64_f32(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_lblt_inverse_u64_f32(FaerMatMut A_inv, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
 
 #endif /* FAER_HIP_NO_FFI_PROTOTYPES */
 
@@ -551,6 +616,9 @@ FAER_HIP_API size_t faer_hip_debug_llt_plan(size_t n, size_t tail_rows, size_t n
  * Writes at most `cap` steps and returns their number. */
 FAER_HIP_API size_t faer_hip_debug_llt_steps(size_t n, size_t la_min, size_t tail_rows, size_t side_rmin, size_t dpanel_rmin, int *codes,
 					     size_t cap);
+/* tests: the calling thread's last lblt_factor_in_place -- out = {blocked panels, rows handled by the leaf, 2 x 2 pivots, host
+ * synchronisations made inside panels (0 for Partial / PartialDiag; one per rook iteration for Rook / RookDiag)} */
+FAER_HIP_API void faer_hip_debug_lblt_last(size_t out[4]);
 FAER_HIP_API int faer_hip_debug_lu_leaf_width(size_t nrows, FaerHipDType dtype, int resident_workgroups);
 /* tests: run every leaf of the partial-pivot LU on the non-cooperative path (the fallback for panels taller than the
  * cooperative kernel can keep resident and for the rerun after an exchange timeout) */
