@@ -107,6 +107,24 @@ class LbltStatus(C.Structure):
     _fields_ = [("tag", C.c_int), ("transposition_count", C.c_size_t)]
 
 
+class PivLltParams(C.Structure):
+    """include/faer_hip.h FaerPivLltParams {block_size}"""
+    _fields_ = [("block_size", C.c_size_t)]
+
+
+class PivLltStatus(C.Structure):
+    """include/faer_hip.h FaerPivLltStatus: tag (0 Ok, 1 NonPositivePivot, 2 Unknown), then the union of ok {rank, transposition_count}
+    and non_positive_pivot {index} (`rank` doubles as the index)"""
+    _fields_ = [("tag", C.c_int), ("rank", C.c_size_t), ("transposition_count", C.c_size_t)]
+
+    @property
+    def index(self):
+        return self.rank
+
+
+PIV_LLT_OK, PIV_LLT_NON_POSITIVE_PIVOT, PIV_LLT_UNKNOWN = 0, 1, 2
+
+
 # include/faer_hip.h FaerPivotingStrategy
 PIVOTING_PARTIAL, PIVOTING_PARTIAL_DIAG, PIVOTING_ROOK, PIVOTING_ROOK_DIAG, PIVOTING_FULL = 0, 1, 2, 3, 4
 PivotingStrategy = {"partial": 0, "partial_diag": 1, "rook": 2, "rook_diag": 3, "full": 4}
@@ -214,6 +232,12 @@ def lib():
         for it in ("u32", "u64"):
             getattr(L, f"libfaer_v0_23_lblt_factor_in_place_{it}_{suf}").restype = LbltStatus
             for name in ("lblt_factor_in_place_scratch", "lblt_solve_in_place_scratch", "lblt_reconstruct_scratch", "lblt_inverse_scratch"):
+                getattr(L, f"libfaer_v0_23_{name}_{it}_{suf}").restype = Layout
+        getattr(L, f"libfaer_v0_23_PivLltParams_{suf}").restype = PivLltParams
+        for it in ("u32", "u64"):
+            getattr(L, f"libfaer_v0_23_piv_llt_factor_in_place_{it}_{suf}").restype = PivLltStatus
+            for name in ("piv_llt_factor_in_place_scratch", "piv_llt_solve_in_place_scratch", "piv_llt_reconstruct_scratch",
+                         "piv_llt_inverse_scratch"):
                 getattr(L, f"libfaer_v0_23_{name}_{it}_{suf}").restype = Layout
     L.libfaer_v0_23_get_global_par.restype = Par
     L.faer_hip_version.restype = C.c_char_p
@@ -1033,6 +1057,63 @@ def debug_lblt_last():
     """(blocked panels, leaf rows, 2 x 2 pivots, host synchronisations inside panels) of this thread's last lblt_factor_in_place"""
     out = (C.c_size_t * 4)()
     lib().faer_hip_debug_lblt_last(out)
+    return tuple(int(v) for v in out)
+
+
+def piv_llt_factor_in_place(a, index_dtype=np.uint64, par=PAR_SEQ, raise_on_error=True):
+    """cholesky/llt_pivoting/factor.rs:47-199: P A P^T = L L^T of the symmetric positive semidefinite matrix in the lower triangle of
+    `a` (the strict upper triangle is never touched); L replaces the lower triangle.  returns (perm_fwd, perm_bwd, rank,
+    transposition_count).  NonPositivePivot raises LltError, or with raise_on_error=False the PivLltStatus is returned instead."""
+    suf, _, _ = _dtype_suffix(a)
+    n = a.shape[0]
+    it = "u64" if np.dtype(index_dtype) == np.uint64 else "u32"
+    fwd = np.zeros(n, dtype=index_dtype)
+    bwd = np.zeros(n, dtype=index_dtype)
+    L = lib()
+    params = getattr(L, f"libfaer_v0_23_PivLltParams_{suf}")()
+    st = getattr(L, f"libfaer_v0_23_piv_llt_factor_in_place_{it}_{suf}")(
+        _mat(a, MatMut), SliceMut(fwd.ctypes.data, n), SliceMut(bwd.ctypes.data, n), par, MemAlloc(None, 0), params)
+    if st.tag != PIV_LLT_OK:
+        if not raise_on_error:
+            return st
+        if st.tag == PIV_LLT_NON_POSITIVE_PIVOT:
+            raise LltError(st.index)
+        raise RuntimeError("PivLltStatus::Unknown")
+    return fwd, bwd, st.rank, st.transposition_count
+
+
+def _piv_llt_call(name, l, perm_fwd, perm_bwd):
+    suf, _, _ = _dtype_suffix(l)
+    it = "u64" if np.dtype(perm_fwd.dtype) == np.uint64 else "u32"
+    n = l.shape[0]
+    return getattr(lib(), f"libfaer_v0_23_{name}_{it}_{suf}"), SliceRef(perm_fwd.ctypes.data, n), SliceRef(perm_bwd.ctypes.data, n)
+
+
+def piv_llt_solve_in_place(l, perm_fwd, perm_bwd, rhs, par=PAR_SEQ):
+    """cholesky/llt_pivoting/solve.rs:13-41: rhs <- A^-1 rhs; `l` as a full-rank piv_llt_factor_in_place leaves it"""
+    fn, pf, pb = _piv_llt_call("piv_llt_solve_in_place", l, perm_fwd, perm_bwd)
+    fn(_mat(l), pf, pb, C.c_int(CONJ_NO), _mat(rhs, MatMut), par, MemAlloc(None, 0))
+    return rhs
+
+
+def piv_llt_reconstruct(out, l, perm_fwd, perm_bwd, par=PAR_SEQ):
+    """cholesky/llt_pivoting/reconstruct.rs: lower(out) <- P^T L L^T P"""
+    fn, pf, pb = _piv_llt_call("piv_llt_reconstruct", l, perm_fwd, perm_bwd)
+    fn(_mat(out, MatMut), _mat(l), pf, pb, par, MemAlloc(None, 0))
+    return out
+
+
+def piv_llt_inverse(out, l, perm_fwd, perm_bwd, par=PAR_SEQ):
+    """cholesky/llt_pivoting/inverse.rs: lower(out) <- A^-1"""
+    fn, pf, pb = _piv_llt_call("piv_llt_inverse", l, perm_fwd, perm_bwd)
+    fn(_mat(out, MatMut), _mat(l), pf, pb, par, MemAlloc(None, 0))
+    return out
+
+
+def debug_piv_llt_last():
+    """(blocked panels, leaf rows, columns factored, host synchronisations inside panels) of this thread's last piv_llt_factor_in_place"""
+    out = (C.c_size_t * 4)()
+    lib().faer_hip_debug_piv_llt_last(out)
     return tuple(int(v) for v in out)
 
 

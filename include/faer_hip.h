@@ -157,6 +157,16 @@ typedef struct FaerLbltStatus {
 	FaerLbltStatus_Tag tag;
 	union { struct { size_t transposition_count; } ok; };
 } FaerLbltStatus;
+/* Cholesky with diagonal pivoting: faer.h:178-180, :432-453, lib.rs:559-571, :656-659 (cholesky/llt_pivoting/factor.rs:5-35) */
+typedef struct FaerPivLltParams { size_t block_size; } FaerPivLltParams;
+typedef enum FaerPivLltStatus_Tag { FaerPivLltStatus_Ok = 0, FaerPivLltStatus_NonPositivePivot = 1, FaerPivLltStatus_Unknown = 2 } FaerPivLltStatus_Tag;
+typedef struct FaerPivLltStatus {
+	FaerPivLltStatus_Tag tag;
+	union {
+		struct { size_t rank; size_t transposition_count; } ok;
+		struct { size_t index; } non_positive_pivot;
+	};
+} FaerPivLltStatus;
 /* faer-ffi/src/lib.rs:796-801; pointers to a real scalar of the matrix dtype (HOST memory), NULL == 0 */
 typedef struct FaerLltRegularization { const void *dynamic_regularization_delta; const void *dynamic_regularization_epsilon; } FaerLltRegularization;
 /* lib.rs:820-828: signs is a slice of i8 (HOST memory, `dim` entries) or a null ptr */
@@ -572,6 +582,56 @@ FAER_HIP_API FaerLayout libfaer_v0_23_lblt_reconstruct_scratch_u64_f32(size_t di
 FAER_HIP_API void libfaer_v0_23_lblt_reconstruct_u64_f32(FaerMatMut A, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
 FAER_HIP_API FaerLayout libfaer_v0_23_lblt_inverse_scratch_u64_f32(size_t dim, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_lblt_inverse_u64_f32(FaerMatMut A_inv, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+/* ---------------------------------------------------------------------------------------------
+ * 2h. PIV_LLT: Cholesky factorization with diagonal pivoting of a symmetric positive semidefinite matrix (faer-ffi/src/lib.rs:
+ *     1076-1188; cholesky/llt_pivoting/factor.rs, solve.rs, reconstruct.rs, inverse.rs; LAPACK's pstrf): P A P^T = L L^T.  Only the
+ *     LOWER triangle of A is read or written; the strict upper triangle is never touched.  perm_fwd[i] = source index of row i of
+ *     P A P^T, perm_bwd its inverse (HOST memory, dim entries).  Every step takes the first strict maximum of the updated diagonal
+ *     as its pivot (ties: the lowest index); a negative or NaN entry of the diagonal of A returns NonPositivePivot{0} with A
+ *     unmodified, a NaN in the updated diagonal at step j NonPositivePivot{j}.  From step 1 on a pivot below tol = eps * dim *
+ *     max diag(A) ends the factorization with Ok{rank = j}: A[j, j] receives that pivot, columns < rank of L, both permutations and
+ *     transposition_count (the number of steps whose pivot differs from the step) are defined, the rest of the lower triangle from
+ *     column rank on is unspecified.  As in the reference the test is not made at step 0: the zero matrix of order >= 2 returns
+ *     NonPositivePivot{1}, of order 1 Ok{rank 1}.  params.block_size is a hint and ignored: the GPU factors lazily updated panels of
+ *     64 columns, two launches per column and no host synchronisation inside a panel, and the last <= 64 rows in one LDS-resident
+ *     workgroup (csrc/piv_llt.hip); the pivot sequence does not depend on the blocking in exact arithmetic.  solve / reconstruct /
+ *     inverse take L as a full-rank factorization leaves it; reconstruct and inverse write the lower triangle of their output only.
+ *     Host or device operands, any strides; par, mem and A_conj are accepted and ignored.  The scratch queries need no device.
+ * --------------------------------------------------------------------------------------------- */
+FAER_HIP_API FaerPivLltParams libfaer_v0_23_PivLltParams_f64(void);
+FAER_HIP_API FaerPivLltParams libfaer_v0_23_PivLltParams_f32(void);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_factor_in_place_scratch_u32_f64(size_t dim, FaerPar par, FaerPivLltParams params);
+FAER_HIP_API FaerPivLltStatus libfaer_v0_23_piv_llt_factor_in_place_u32_f64(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPivLltParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_solve_in_place_scratch_u32_f64(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_solve_in_place_u32_f64(FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerConj A_conj, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_reconstruct_scratch_u32_f64(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_reconstruct_u32_f64(FaerMatMut A, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_inverse_scratch_u32_f64(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_inverse_u32_f64(FaerMatMut A_inv, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_factor_in_place_scratch_u32_f32(size_t dim, FaerPar par, FaerPivLltParams params);
+FAER_HIP_API FaerPivLltStatus libfaer_v0_23_piv_llt_factor_in_place_u32_f32(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPivLltParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_solve_in_place_scratch_u32_f32(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_solve_in_place_u32_f32(FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerConj A_conj, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_reconstruct_scratch_u32_f32(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_reconstruct_u32_f32(FaerMatMut A, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_inverse_scratch_u32_f32(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_inverse_u32_f32(FaerMatMut A_inv, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_factor_in_place_scratch_u64_f64(size_t dim, FaerPar par, FaerPivLltParams params);
+FAER_HIP_API FaerPivLltStatus libfaer_v0_23_piv_llt_factor_in_place_u64_f64(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPivLltParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_solve_in_place_scratch_u64_f64(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_solve_in_place_u64_f64(FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerConj A_conj, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_reconstruct_scratch_u64_f64(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_reconstruct_u64_f64(FaerMatMut A, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_inverse_scratch_u64_f64(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_inverse_u64_f64(FaerMatMut A_inv, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_factor_in_place_scratch_u64_f32(size_t dim, FaerPar par, FaerPivLltParams params);
+FAER_HIP_API FaerPivLltStatus libfaer_v0_23_piv_llt_factor_in_place_u64_f32(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPivLltParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_solve_in_place_scratch_u64_f32(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_solve_in_place_u64_f32(FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerConj A_conj, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_reconstruct_scratch_u64_f32(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_reconstruct_u64_f32(FaerMatMut A, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_inverse_scratch_u64_f32(size_t dim, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_piv_llt_inverse_u64_f32(FaerMatMut A_inv, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
 
 #endif /* FAER_HIP_NO_FFI_PROTOTYPES */
 
@@ -619,6 +679,9 @@ FAER_HIP_API size_t faer_hip_debug_llt_steps(size_t n, size_t la_min, size_t tai
 /* tests: the calling thread's last lblt_factor_in_place -- out = {blocked panels, rows handled by the leaf, 2 x 2 pivots, host
  * synchronisations made inside panels (0 for Partial / PartialDiag; one per rook iteration for Rook / RookDiag)} */
 FAER_HIP_API void faer_hip_debug_lblt_last(size_t out[4]);
+/* tests: the calling thread's last piv_llt_factor_in_place -- out = {blocked panels, rows handled by the leaf (0: the factorization
+ * ended in a panel), columns of L factored (the rank), host synchronisations made inside panels (0)} */
+FAER_HIP_API void faer_hip_debug_piv_llt_last(size_t out[4]);
 FAER_HIP_API int faer_hip_debug_lu_leaf_width(size_t nrows, FaerHipDType dtype, int resident_workgroups);
 /* tests: run every leaf of the partial-pivot LU on the non-cooperative path (the fallback for panels taller than the
  * cooperative kernel can keep resident and for the rerun after an exchange timeout) */
