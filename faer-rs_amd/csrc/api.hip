@@ -4,21 +4,11 @@
 #include <atomic>
 
 #include "common.h"
+#include "perm.h"
 
 using namespace fh;
 
 namespace {
-
-template <typename T> MatV<const T> view(FaerMatRef m)
-{
-	return MatV<const T>{static_cast<const T *>(m.ptr), (idx_t) m.nrows, (idx_t) m.ncols, (idx_t) m.row_stride,
-			     (idx_t) m.col_stride};
-}
-template <typename T> MatV<T> view(FaerMatMut m)
-{
-	return MatV<T>{static_cast<T *>(m.ptr), (idx_t) m.nrows, (idx_t) m.ncols, (idx_t) m.row_stride,
-		       (idx_t) m.col_stride};
-}
 
 std::atomic<int> g_par_tag{(int) FaerParTag_Rayon};
 std::atomic<size_t> g_par_threads{0};
@@ -116,9 +106,7 @@ template <typename T> void ldlt_solve_api(FaerMatRef L, FaerVecRef D, FaerMatMut
 {
 	FH_CHECK(L.nrows == L.ncols && rhs.nrows == L.nrows && D.len == L.nrows, "ldlt solve: dimension mismatch");
 	Staged<const T> l(view<T>(L), true, false);
-	// D as an n x 1 view (stride in elements)
-	FaerMatRef Dm{D.ptr, D.len, 1, D.stride, 0};
-	Staged<const T> d(view<T>(Dm), true, false);
+	Staged<const T> d(vview<T>(D), true, false);
 	Staged<T> x(view<T>(rhs), true, true);
 	trsm_lower_dev<T>(l.dev, true, x.dev);
 	scale_rows_recip_dev<T>(x.dev, d.dev.p, d.dev.rs);
@@ -138,8 +126,6 @@ template <typename T> void llt_solve_api(FaerMatRef L, FaerMatMut rhs)
 template <typename T, typename I> FaerPartialPivLuStatus lu_api(FaerMatMut A, FaerSliceMut pf, FaerSliceMut pb)
 {
 	const idx_t m = (idx_t) A.nrows;
-	FH_CHECK((idx_t) pf.len == m && (idx_t) pb.len == m, "partial_piv_lu: perm slices must have nrows entries");
-	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "partial_piv_lu: perm slices must be host memory");
 	std::vector<idx_t> perm((size_t) m), perm_inv((size_t) m);
 	long nt;
 	{
@@ -148,11 +134,7 @@ template <typename T, typename I> FaerPartialPivLuStatus lu_api(FaerMatMut A, Fa
 		if (nt < 0)
 			a.writeback = false; // Unknown (exchange timeout without room for the rerun): a host operand keeps its input
 	}
-	I *f = static_cast<I *>(pf.ptr), *b = static_cast<I *>(pb.ptr);
-	for (idx_t i = 0; i < m; ++i) {
-		f[i] = (I) perm[(size_t) i];
-		b[i] = (I) perm_inv[(size_t) i];
-	}
+	store_perm<I>("partial_piv_lu", pf, pb, perm.data(), perm_inv.data(), m);
 	FaerPartialPivLuStatus st;
 	memset(&st, 0, sizeof(st));
 	st.tag = nt >= 0 ? FaerPartialPivLuStatus_Ok : FaerPartialPivLuStatus_Unknown; // Unknown: exchange timeout (getrf.hip)
@@ -213,48 +195,35 @@ template <typename T> void apply_hh_api(FaerMatRef V, FaerMatRef H, FaerMatMut r
 	apply_householder_sequence_left_dev<T>(v.dev, h.dev, x.dev, transpose);
 }
 
-// rhs[i, :] <- rhs[perm[i], :]   (perm/mod.rs:256-294 permute_rows with dst == a copy of src); perm is a HOST slice
-template <typename T, typename I> void permute_rows_dev_api(MatV<T> X, const I *perm_host)
-{
-	const idx_t n = X.nrows, k = X.ncols;
-	if (n == 0 || k == 0)
-		return;
-	std::vector<idx_t> p64((size_t) n);
-	for (idx_t i = 0; i < n; ++i) {
-		p64[(size_t) i] = (idx_t) perm_host[i];
-		FH_CHECK(p64[(size_t) i] >= 0 && p64[(size_t) i] < n, "permutation index out of range");
-	}
-	Scratch pb((size_t) n * sizeof(idx_t)), tb((size_t) n * (size_t) k * sizeof(T));
-	FH_HIP(hipMemcpyAsync(pb.p, p64.data(), (size_t) n * sizeof(idx_t), hipMemcpyHostToDevice, ctx().stream));
-	MatV<T> tmp{tb.as<T>(), n, k, 1, n};
-	gather_rows_dev<T>(tmp, X.c(), pb.as<idx_t>());
-	copy_dev<T>(X, tmp.c());
-	ctx().sync(); // p64 and the scratch buffers go out of scope
-}
-
 // lu/partial_pivoting/solve.rs:20-50 and :52-80
 template <typename T, typename I>
 void lu_solve_api(FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, bool transpose)
 {
 	const size_t n = L.nrows;
-	FH_CHECK(L.ncols == n && U.nrows == n && U.ncols == n && rhs.nrows == n && pf.len >= n && pb.len >= n,
-		 "partial_piv_lu solve: dimension mismatch");
-	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "partial_piv_lu solve: perm slices must be host memory");
+	FH_CHECK(L.ncols == n && U.nrows == n && U.ncols == n && rhs.nrows == n, "partial_piv_lu solve: dimension mismatch");
+	check_perm_slice("partial_piv_lu solve", transpose ? pf : pb, (idx_t) n); // (the one that is not used)
+	DevPerm perm("partial_piv_lu solve", transpose ? pb : pf, (idx_t) n, I{});
 	Staged<const T> l(view<T>(L), true, false), u(view<T>(U), true, false);
 	Staged<T> x(view<T>(rhs), true, true);
 	if (!transpose) {
-		permute_rows_dev_api<T, I>(x.dev, static_cast<const I *>(pf.ptr));
+		permute_rows<T>(x.dev, perm);
 		trsm_lower_dev<T>(l.dev, true, x.dev);
 		trsm_upper_dev<T>(u.dev, false, x.dev);
 	} else {
 		trsm_lower_dev<T>(u.dev.t(), false, x.dev);
 		trsm_upper_dev<T>(l.dev.t(), true, x.dev);
-		permute_rows_dev_api<T, I>(x.dev, static_cast<const I *>(pb.ptr)); // the inverse permutation
+		permute_rows<T>(x.dev, perm); // the inverse permutation
 	}
 }
 
+// the three read-only operands of the QR solver side, staged once
+template <typename T> struct QrFactors {
+	Staged<const T> qb, qc, r;
+	QrFactors(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R) : qb(view<T>(Qb), true, false), qc(view<T>(Qc), true, false), r(view<T>(R), true, false) {}
+};
+
 // qr/no_pivoting/solve.rs:38-75 (lstsq / square) and :140-175 (transpose)
-template <typename T> void qr_solve_api(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerMatMut rhs, bool transpose, bool square)
+void qr_solve_check(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerMatMut rhs, bool transpose, bool square)
 {
 	const size_t m = Qb.nrows, n = Qb.ncols;
 	const size_t size = m < n ? m : n;
@@ -262,19 +231,26 @@ template <typename T> void qr_solve_api(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef
 		 "qr solve: dimension mismatch");
 	if (square || transpose)
 		FH_CHECK(m == n && R.nrows == n, "qr solve: the factorization must be square");
-	Staged<const T> qb(view<T>(Qb), true, false), qc(view<T>(Qc), true, false), r(view<T>(R), true, false);
-	Staged<T> x(view<T>(rhs), true, true);
-	MatV<const T> Rtop = r.dev.sub(0, 0, (idx_t) size, (idx_t) n);
+}
+template <typename T> void qr_solve_dev(MatV<const T> Qb, MatV<const T> Qc, MatV<const T> R, MatV<T> X, bool transpose)
+{
+	const idx_t n = Qb.ncols; // (== min(nrows, ncols): qr_solve_check)
+	MatV<const T> Rtop = R.sub(0, 0, n, n);
 	if (!transpose) {
-		apply_householder_sequence_left_dev<T>(qb.dev, qc.dev, x.dev, true); // Q^H rhs
-		trsm_upper_dev<T>(Rtop, false, x.dev.sub(0, 0, (idx_t) size, x.dev.ncols));
+		apply_householder_sequence_left_dev<T>(Qb, Qc, X, true); // Q^H rhs
+		trsm_upper_dev<T>(Rtop, false, X.sub(0, 0, n, X.ncols));
 	} else {
-		trsm_lower_dev<T>(Rtop.t(), false, x.dev);
-		apply_householder_sequence_left_dev<T>(qb.dev, qc.dev, x.dev, false); // Q rhs
+		trsm_lower_dev<T>(Rtop.t(), false, X);
+		apply_householder_sequence_left_dev<T>(Qb, Qc, X, false); // Q rhs
 	}
 }
-
-FaerLayout layout(size_t bytes, size_t align) { return FaerLayout{bytes, align}; }
+template <typename T> void qr_solve_api(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerMatMut rhs, bool transpose, bool square)
+{
+	qr_solve_check(Qb, Qc, R, rhs, transpose, square);
+	QrFactors<T> f(Qb, Qc, R);
+	Staged<T> x(view<T>(rhs), true, true);
+	qr_solve_dev<T>(f.qb.dev, f.qc.dev, f.r.dev, x.dev, transpose);
+}
 
 // ---- triangular inverse (triangular_inverse.rs:43-230): dst's other triangle (and, unit: its diagonal) is untouched
 template <typename T> void tri_inverse_api(FaerMatMut Out, FaerMatRef Tm, bool upper, bool unit)
@@ -317,8 +293,7 @@ template <typename T> void ldlt_reconstruct_api(FaerMatMut Out, FaerMatRef L, Fa
 	const idx_t n = (idx_t) L.nrows;
 	FH_CHECK(L.nrows == L.ncols && Out.nrows == L.nrows && Out.ncols == L.nrows && D.len == L.nrows, "ldlt reconstruct: dimension mismatch");
 	Staged<const T> l(view<T>(L), true, false);
-	FaerMatRef Dm{D.ptr, D.len, 1, D.stride, 0};
-	Staged<const T> d(view<T>(Dm), true, false);
+	Staged<const T> d(vview<T>(D), true, false);
 	Staged<T> o(view<T>(Out), true, true);
 	Scratch wb((size_t) n * (size_t) n * sizeof(T) + 256);
 	MatV<T> LxD{wb.as<T>(), n, n, 1, n};
@@ -333,8 +308,7 @@ template <typename T> void ldlt_inverse_api(FaerMatMut Out, FaerMatRef L, FaerVe
 	const idx_t n = (idx_t) L.nrows;
 	FH_CHECK(L.nrows == L.ncols && Out.nrows == L.nrows && Out.ncols == L.nrows && D.len == L.nrows, "ldlt inverse: dimension mismatch");
 	Staged<const T> l(view<T>(L), true, false);
-	FaerMatRef Dm{D.ptr, D.len, 1, D.stride, 0};
-	Staged<const T> d(view<T>(Dm), true, false);
+	Staged<const T> d(vview<T>(D), true, false);
 	Staged<T> o(view<T>(Out), true, true);
 	Scratch wb((size_t) n * (size_t) n * sizeof(T) + 256);
 	MatV<T> W{wb.as<T>(), n, n, 1, n};
@@ -344,31 +318,20 @@ template <typename T> void ldlt_inverse_api(FaerMatMut Out, FaerMatRef L, FaerVe
 	ctx().sync();
 }
 
-template <typename I> static void upload_perm(Scratch &buf, const void *perm_host, idx_t n)
-{
-	std::vector<idx_t> p64((size_t) n);
-	for (idx_t i = 0; i < n; ++i) {
-		p64[(size_t) i] = (idx_t) static_cast<const I *>(perm_host)[i];
-		FH_CHECK(p64[(size_t) i] >= 0 && p64[(size_t) i] < n, "permutation index out of range");
-	}
-	FH_HIP(hipMemcpyAsync(buf.p, p64.data(), (size_t) n * sizeof(idx_t), hipMemcpyHostToDevice, ctx().stream));
-	ctx().sync(); // p64 goes out of scope
-}
-
 // lu/partial_pivoting/reconstruct.rs:17-83: out = P^-1 (L U)
 template <typename T, typename I> void lu_reconstruct_api(FaerMatMut Out, FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb)
 {
 	const idx_t m = (idx_t) L.nrows, n = (idx_t) U.ncols;
 	const idx_t size = m < n ? m : n;
-	FH_CHECK(Out.nrows == L.nrows && Out.ncols == U.ncols && (idx_t) L.ncols >= size && (idx_t) U.nrows >= size && pf.len >= L.nrows &&
-			 pb.len >= L.nrows,
+	FH_CHECK(Out.nrows == L.nrows && Out.ncols == U.ncols && (idx_t) L.ncols >= size && (idx_t) U.nrows >= size,
 		 "partial_piv_lu reconstruct: dimension mismatch");
-	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "partial_piv_lu reconstruct: perm slices must be host memory");
+	check_perm_slice("partial_piv_lu reconstruct", pf, m);
+	DevPerm perm_bwd("partial_piv_lu reconstruct", pb, m, I{});
 	if (m == 0 || n == 0)
 		return;
 	Staged<const T> l(view<T>(L), true, false), u(view<T>(U), true, false);
 	Staged<T> o(view<T>(Out), false, true);
-	Scratch tb((size_t) m * (size_t) n * sizeof(T)), pbuf((size_t) m * sizeof(idx_t));
+	Scratch tb((size_t) m * (size_t) n * sizeof(T));
 	MatV<T> tmp{tb.as<T>(), m, n, 1, m};
 	matmul_triangular_dev<T>(tmp.sub(0, 0, size, size), 0, false, l.dev.sub(0, 0, size, size), 5, u.dev.sub(0, 0, size, size), 2, (T) 1);
 	if (m > n)
@@ -377,8 +340,7 @@ template <typename T, typename I> void lu_reconstruct_api(FaerMatMut Out, FaerMa
 	if (m < n)
 		matmul_triangular_dev<T>(tmp.sub(0, size, size, n - size), 0, false, l.dev.sub(0, 0, size, size), 5, u.dev.sub(0, size, size, n - size), 0,
 					 (T) 1);
-	upload_perm<I>(pbuf, pb.ptr, m); // permute_rows(out, tmp, perm.inverse()): out[i, :] = tmp[perm_bwd[i], :]
-	gather_rows_dev<T>(o.dev, tmp.c(), pbuf.as<idx_t>());
+	gather_rows_dev<T>(o.dev, tmp.c(), perm_bwd.dev()); // permute_rows(out, tmp, perm.inverse()): out[i, :] = tmp[perm_bwd[i], :]
 	ctx().sync();
 }
 
@@ -386,52 +348,66 @@ template <typename T, typename I> void lu_reconstruct_api(FaerMatMut Out, FaerMa
 template <typename T, typename I> void lu_inverse_api(FaerMatMut Out, FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb)
 {
 	const idx_t n = (idx_t) L.ncols;
-	FH_CHECK((idx_t) L.nrows == n && (idx_t) U.nrows == n && (idx_t) U.ncols == n && (idx_t) Out.nrows == n && (idx_t) Out.ncols == n &&
-			 (idx_t) pf.len >= n && (idx_t) pb.len >= n,
+	FH_CHECK((idx_t) L.nrows == n && (idx_t) U.nrows == n && (idx_t) U.ncols == n && (idx_t) Out.nrows == n && (idx_t) Out.ncols == n,
 		 "partial_piv_lu inverse: dimension mismatch");
-	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "partial_piv_lu inverse: perm slices must be host memory");
+	check_perm_slice("partial_piv_lu inverse", pf, n);
+	DevPerm perm_bwd("partial_piv_lu inverse", pb, n, I{});
 	if (n == 0)
 		return;
 	Staged<const T> l(view<T>(L), true, false), u(view<T>(U), true, false);
 	Staged<T> o(view<T>(Out), false, true);
-	Scratch tb((size_t) n * (size_t) n * sizeof(T)), pbuf((size_t) n * sizeof(idx_t));
+	Scratch tb((size_t) n * (size_t) n * sizeof(T));
 	MatV<T> tmp{tb.as<T>(), n, n, 1, n};
 	tri_invert_lower_dev<T>(o.dev, l.dev, true);	  // strict lower part of out
 	tri_invert_lower_dev<T>(o.dev.t(), u.dev.t(), false); // upper part (with diagonal) of out
 	matmul_triangular_dev<T>(tmp, 0, false, o.dev.c(), 2, o.dev.c(), 5, (T) 1);
-	upload_perm<I>(pbuf, pb.ptr, n); // permute_cols(out, tmp, perm.inverse()): out[:, j] = tmp[:, perm_bwd[j]]
-	gather_rows_dev<T>(o.dev.t(), tmp.t().c(), pbuf.as<idx_t>());
+	gather_rows_dev<T>(o.dev.t(), tmp.t().c(), perm_bwd.dev()); // permute_cols(out, tmp, perm.inverse()): out[:, j] = tmp[:, perm_bwd[j]]
 	ctx().sync();
 }
 
 // qr/no_pivoting/reconstruct.rs:18-52: out = Q [R; 0]
-template <typename T> void qr_reconstruct_api(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R)
+void qr_reconstruct_check(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R)
 {
 	const idx_t m = (idx_t) Qb.nrows, n = (idx_t) R.ncols;
 	const idx_t size = m < n ? m : n;
 	FH_CHECK((idx_t) Out.nrows == m && (idx_t) Out.ncols == n && (idx_t) Qb.ncols == size && (idx_t) Qc.ncols == size && (idx_t) R.nrows == size &&
 			 Qc.nrows > 0,
 		 "qr reconstruct: dimension mismatch");
-	Staged<const T> v(view<T>(Qb), true, false), h(view<T>(Qc), true, false), r(view<T>(R), true, false);
+}
+template <typename T> void qr_reconstruct_dev(MatV<T> Out, MatV<const T> Qb, MatV<const T> Qc, MatV<const T> R)
+{
+	zero_then_upper_dev<T>(Out, &R);
+	apply_householder_sequence_left_dev<T>(Qb, Qc, Out, false);
+}
+template <typename T> void qr_reconstruct_api(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R)
+{
+	qr_reconstruct_check(Out, Qb, Qc, R);
+	QrFactors<T> f(Qb, Qc, R);
 	Staged<T> o(view<T>(Out), false, true);
-	MatV<const T> Rv = r.dev;
-	zero_then_upper_dev<T>(o.dev, &Rv);
-	apply_householder_sequence_left_dev<T>(v.dev, h.dev, o.dev, false);
+	qr_reconstruct_dev<T>(o.dev, f.qb.dev, f.qc.dev, f.r.dev);
 }
 
 // qr/no_pivoting/inverse.rs:17-58: out = R^-1 Q^H
-template <typename T> void qr_inverse_api(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R)
+void qr_inverse_check(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R)
 {
 	const idx_t n = (idx_t) Qb.ncols;
 	FH_CHECK(Qc.nrows > 0 && (idx_t) Qb.nrows == n && (idx_t) Qc.ncols == n && (idx_t) R.nrows == n && (idx_t) R.ncols == n &&
 			 (idx_t) Out.nrows == n && (idx_t) Out.ncols == n,
 		 "qr inverse: dimension mismatch");
-	Staged<const T> v(view<T>(Qb), true, false), h(view<T>(Qc), true, false), r(view<T>(R), true, false);
-	Staged<T> o(view<T>(Out), false, true);
-	zero_then_upper_dev<T>(o.dev, nullptr);
-	tri_invert_lower_dev<T>(o.dev.t(), r.dev.t(), false);
+}
+template <typename T> void qr_inverse_dev(MatV<T> Out, MatV<const T> Qb, MatV<const T> Qc, MatV<const T> R)
+{
+	zero_then_upper_dev<T>(Out, nullptr);
+	tri_invert_lower_dev<T>(Out.t(), R.t(), false);
 	// out <- out Q^H  ==  (Q out^T)^T   (householder.rs:836-854)
-	apply_householder_sequence_left_dev<T>(v.dev, h.dev, o.dev.t(), false);
+	apply_householder_sequence_left_dev<T>(Qb, Qc, Out.t(), false);
+}
+template <typename T> void qr_inverse_api(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R)
+{
+	qr_inverse_check(Out, Qb, Qc, R);
+	QrFactors<T> f(Qb, Qc, R);
+	Staged<T> o(view<T>(Out), false, true);
+	qr_inverse_dev<T>(o.dev, f.qb.dev, f.qc.dev, f.r.dev);
 }
 
 // householder.rs:813-854: M <- M Q (transpose == false) or M Q^H (transpose == true), as left applications on M^T
@@ -449,24 +425,14 @@ template <typename T, typename I>
 FaerFullPivLuStatus full_lu_api(FaerMatMut A, FaerSliceMut rpf, FaerSliceMut rpb, FaerSliceMut cpf, FaerSliceMut cpb)
 {
 	const idx_t m = (idx_t) A.nrows, n = (idx_t) A.ncols;
-	FH_CHECK((idx_t) rpf.len == m && (idx_t) rpb.len == m && (idx_t) cpf.len == n && (idx_t) cpb.len == n,
-		 "full_piv_lu: perm slices must have nrows / ncols entries");
-	FH_CHECK(!is_device_ptr(rpf.ptr) && !is_device_ptr(rpb.ptr) && !is_device_ptr(cpf.ptr) && !is_device_ptr(cpb.ptr),
-		 "full_piv_lu: perm slices must be host memory");
 	std::vector<idx_t> rp((size_t) m), rpi((size_t) m), cp((size_t) n), cpi((size_t) n);
 	long nt;
 	{
 		Staged<T> a(view<T>(A), true, true);
 		nt = full_piv_lu_dev<T>(a.dev, rp.data(), rpi.data(), cp.data(), cpi.data());
 	}
-	for (idx_t i = 0; i < m; ++i) {
-		static_cast<I *>(rpf.ptr)[i] = (I) rp[(size_t) i];
-		static_cast<I *>(rpb.ptr)[i] = (I) rpi[(size_t) i];
-	}
-	for (idx_t j = 0; j < n; ++j) {
-		static_cast<I *>(cpf.ptr)[j] = (I) cp[(size_t) j];
-		static_cast<I *>(cpb.ptr)[j] = (I) cpi[(size_t) j];
-	}
+	store_perm<I>("full_piv_lu", rpf, rpb, rp.data(), rpi.data(), m);
+	store_perm<I>("full_piv_lu", cpf, cpb, cp.data(), cpi.data(), n);
 	FaerFullPivLuStatus st;
 	memset(&st, 0, sizeof(st));
 	st.tag = FaerFullPivLuStatus_Ok;
@@ -480,23 +446,23 @@ void full_lu_solve_api(FaerMatRef L, FaerMatRef U, FaerSliceRef rpf, FaerSliceRe
 		       bool transpose)
 {
 	const size_t n = L.nrows;
-	FH_CHECK(L.ncols == n && U.nrows == n && U.ncols == n && rhs.nrows == n && rpf.len >= n && rpb.len >= n && cpf.len >= n && cpb.len >= n,
-		 "full_piv_lu solve: dimension mismatch");
-	FH_CHECK(!is_device_ptr(rpf.ptr) && !is_device_ptr(rpb.ptr) && !is_device_ptr(cpf.ptr) && !is_device_ptr(cpb.ptr),
-		 "full_piv_lu solve: perm slices must be host memory");
+	const char *who = "full_piv_lu solve";
+	FH_CHECK(L.ncols == n && U.nrows == n && U.ncols == n && rhs.nrows == n, "full_piv_lu solve: dimension mismatch");
+	check_perm_slice(who, transpose ? rpf : rpb, (idx_t) n); // (the two that are not used)
+	check_perm_slice(who, transpose ? cpb : cpf, (idx_t) n);
+	// A x = b: row_perm, then col_perm.inverse(); A^T x = b: col_perm, then row_perm.inverse()
+	DevPerm first(who, transpose ? cpf : rpf, (idx_t) n, I{}), last(who, transpose ? rpb : cpb, (idx_t) n, I{});
 	Staged<const T> l(view<T>(L), true, false), u(view<T>(U), true, false);
 	Staged<T> x(view<T>(rhs), true, true);
+	permute_rows<T>(x.dev, first);
 	if (!transpose) {
-		permute_rows_dev_api<T, I>(x.dev, static_cast<const I *>(rpf.ptr));
 		trsm_lower_dev<T>(l.dev, true, x.dev);
 		trsm_upper_dev<T>(u.dev, false, x.dev);
-		permute_rows_dev_api<T, I>(x.dev, static_cast<const I *>(cpb.ptr)); // col_perm.inverse()
 	} else {
-		permute_rows_dev_api<T, I>(x.dev, static_cast<const I *>(cpf.ptr));
 		trsm_lower_dev<T>(u.dev.t(), false, x.dev);
 		trsm_upper_dev<T>(l.dev.t(), true, x.dev);
-		permute_rows_dev_api<T, I>(x.dev, static_cast<const I *>(rpb.ptr)); // row_perm.inverse()
 	}
+	permute_rows<T>(x.dev, last);
 }
 
 // evd/tridiag.rs:274-299
@@ -544,8 +510,6 @@ template <typename T, typename I> FaerColPivQrStatus colpiv_qr_api(FaerMatMut A,
 	const idx_t n = (idx_t) A.ncols;
 	const size_t size = A.nrows < A.ncols ? A.nrows : A.ncols;
 	FH_CHECK(Q.nrows > 0 && Q.ncols == size, "colpiv_qr: Q_coeff must be block_size x min(nrows, ncols)");
-	FH_CHECK((idx_t) pf.len == n && (idx_t) pb.len == n, "colpiv_qr: perm slices must have ncols entries");
-	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "colpiv_qr: perm slices must be host memory");
 	std::vector<idx_t> cp((size_t) n), cpi((size_t) n);
 	long nt;
 	{
@@ -553,10 +517,7 @@ template <typename T, typename I> FaerColPivQrStatus colpiv_qr_api(FaerMatMut A,
 		Staged<T> q(view<T>(Q), false, true);
 		nt = colpiv_qr_dev<T>(a.dev, q.dev, cp.data(), cpi.data());
 	}
-	for (idx_t j = 0; j < n; ++j) {
-		static_cast<I *>(pf.ptr)[j] = (I) cp[(size_t) j];
-		static_cast<I *>(pb.ptr)[j] = (I) cpi[(size_t) j];
-	}
+	store_perm<I>("colpiv_qr", pf, pb, cp.data(), cpi.data(), n);
 	FaerColPivQrStatus st;
 	memset(&st, 0, sizeof(st));
 	st.tag = FaerColPivQrStatus_Ok;
@@ -568,33 +529,17 @@ template <typename T, typename I> FaerColPivQrStatus colpiv_qr_api(FaerMatMut A,
 template <typename T, typename I>
 void colpiv_qr_solve_api(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, bool transpose, bool square)
 {
-	const size_t m = Qb.nrows, n = Qb.ncols;
-	const size_t size = m < n ? m : n;
-	FH_CHECK(pf.len >= n && pb.len >= n && !is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "colpiv_qr solve: perm slices (host memory, ncols entries)");
-	if (!transpose) {
-		qr_solve_api<T>(Qb, Qc, R, rhs, false, square);
-		Staged<T> x(view<T>(rhs), true, true);
-		permute_rows_dev_api<T, I>(x.dev.sub(0, 0, (idx_t) size, x.dev.ncols), static_cast<const I *>(pb.ptr)); // col_perm.inverse()
-	} else {
-		{
-			Staged<T> x(view<T>(rhs), true, true);
-			permute_rows_dev_api<T, I>(x.dev, static_cast<const I *>(pf.ptr));
-		}
-		qr_solve_api<T>(Qb, Qc, R, rhs, true, true);
-	}
-}
-
-// out(i, j) = tmp(rmap[i], cmap[j]) with host index maps (two gathers through a second temporary)
-template <typename T, typename I> static void gather_rows_cols(MatV<T> out, MatV<T> tmp, const void *rmap, const void *cmap)
-{
-	const idx_t m = out.nrows, n = out.ncols;
-	Scratch rb((size_t) m * sizeof(idx_t) + 256), cb((size_t) n * sizeof(idx_t) + 256), t2((size_t) m * (size_t) n * sizeof(T) + 256);
-	upload_perm<I>(rb, rmap, m);
-	upload_perm<I>(cb, cmap, n);
-	MatV<T> tmp2{t2.as<T>(), m, n, 1, m};
-	gather_rows_dev<T>(tmp2, tmp.c(), rb.as<idx_t>());
-	gather_rows_dev<T>(out.t(), tmp2.t().c(), cb.as<idx_t>());
-	ctx().sync();
+	const idx_t n = (idx_t) Qb.ncols;
+	check_perm_slice("colpiv_qr solve", transpose ? pb : pf, n); // (the one that is not used)
+	qr_solve_check(Qb, Qc, R, rhs, transpose, square);
+	DevPerm perm("colpiv_qr solve", transpose ? pf : pb, n, I{});
+	QrFactors<T> f(Qb, Qc, R);
+	Staged<T> x(view<T>(rhs), true, true);
+	if (transpose)
+		permute_rows<T>(x.dev, perm);
+	qr_solve_dev<T>(f.qb.dev, f.qc.dev, f.r.dev, x.dev, transpose);
+	if (!transpose)
+		permute_rows<T>(x.dev.sub(0, 0, n, x.dev.ncols), perm); // col_perm.inverse() on the rows of the solution
 }
 
 // lu/full_pivoting/reconstruct.rs: out(i, j) = (L U)(row_perm_inv[i], col_perm_inv[j])
@@ -605,10 +550,9 @@ void full_lu_reconstruct_api(FaerMatMut Out, FaerMatRef L, FaerMatRef U, FaerSli
 	(void) cpf;
 	const idx_t m = (idx_t) L.nrows, n = (idx_t) U.ncols;
 	const idx_t size = m < n ? m : n;
-	FH_CHECK((idx_t) Out.nrows == m && (idx_t) Out.ncols == n && (idx_t) L.ncols >= size && (idx_t) U.nrows >= size && (idx_t) rpb.len >= m &&
-			 (idx_t) cpb.len >= n,
+	FH_CHECK((idx_t) Out.nrows == m && (idx_t) Out.ncols == n && (idx_t) L.ncols >= size && (idx_t) U.nrows >= size,
 		 "full_piv_lu reconstruct: dimension mismatch");
-	FH_CHECK(!is_device_ptr(rpb.ptr) && !is_device_ptr(cpb.ptr), "full_piv_lu reconstruct: perm slices must be host memory");
+	DevPerm rows("full_piv_lu reconstruct", rpb, m, I{}), cols("full_piv_lu reconstruct", cpb, n, I{});
 	if (m == 0 || n == 0)
 		return;
 	Staged<const T> l(view<T>(L), true, false), u(view<T>(U), true, false);
@@ -622,7 +566,8 @@ void full_lu_reconstruct_api(FaerMatMut Out, FaerMatRef L, FaerMatRef U, FaerSli
 	if (m < n)
 		matmul_triangular_dev<T>(tmp.sub(0, size, size, n - size), 0, false, l.dev.sub(0, 0, size, size), 5, u.dev.sub(0, size, size, n - size), 0,
 					 (T) 1);
-	gather_rows_cols<T, I>(o.dev, tmp, rpb.ptr, cpb.ptr);
+	gather_rows_cols<T>(o.dev, tmp, rows, cols);
+	ctx().sync();
 }
 
 // lu/full_pivoting/inverse.rs: out(i, j) = (U^-1 L^-1)(col_perm_inv[i], row_perm_inv[j])
@@ -632,10 +577,9 @@ void full_lu_inverse_api(FaerMatMut Out, FaerMatRef L, FaerMatRef U, FaerSliceRe
 	(void) rpf;
 	(void) cpf;
 	const idx_t n = (idx_t) L.ncols;
-	FH_CHECK((idx_t) L.nrows == n && (idx_t) U.nrows == n && (idx_t) U.ncols == n && (idx_t) Out.nrows == n && (idx_t) Out.ncols == n &&
-			 (idx_t) rpb.len >= n && (idx_t) cpb.len >= n,
+	FH_CHECK((idx_t) L.nrows == n && (idx_t) U.nrows == n && (idx_t) U.ncols == n && (idx_t) Out.nrows == n && (idx_t) Out.ncols == n,
 		 "full_piv_lu inverse: dimension mismatch");
-	FH_CHECK(!is_device_ptr(rpb.ptr) && !is_device_ptr(cpb.ptr), "full_piv_lu inverse: perm slices must be host memory");
+	DevPerm rows("full_piv_lu inverse", cpb, n, I{}), cols("full_piv_lu inverse", rpb, n, I{});
 	if (n == 0)
 		return;
 	Staged<const T> l(view<T>(L), true, false), u(view<T>(U), true, false);
@@ -645,7 +589,8 @@ void full_lu_inverse_api(FaerMatMut Out, FaerMatRef L, FaerMatRef U, FaerSliceRe
 	tri_invert_lower_dev<T>(o.dev, l.dev, true);
 	tri_invert_lower_dev<T>(o.dev.t(), u.dev.t(), false);
 	matmul_triangular_dev<T>(tmp, 0, false, o.dev.c(), 2, o.dev.c(), 5, (T) 1);
-	gather_rows_cols<T, I>(o.dev, tmp, cpb.ptr, rpb.ptr);
+	gather_rows_cols<T>(o.dev, tmp, rows, cols);
+	ctx().sync();
 }
 
 // qr/col_pivoting/reconstruct.rs: (Q R) with its columns permuted back; inverse.rs: rows of R^-1 Q^H permuted back
@@ -653,21 +598,23 @@ template <typename T, typename I>
 void colpiv_qr_reconstruct_api(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerSliceRef pf, FaerSliceRef pb)
 {
 	(void) pf;
-	const idx_t n = (idx_t) R.ncols;
-	FH_CHECK((idx_t) pb.len >= n && !is_device_ptr(pb.ptr), "colpiv_qr reconstruct: perm slices (host memory, ncols entries)");
-	qr_reconstruct_api<T>(Out, Qb, Qc, R);
-	Staged<T> o(view<T>(Out), true, true);
-	permute_rows_dev_api<T, I>(o.dev.t(), static_cast<const I *>(pb.ptr)); // permute_cols_in_place(out, col_perm.inverse())
+	qr_reconstruct_check(Out, Qb, Qc, R);
+	DevPerm perm_bwd("colpiv_qr reconstruct", pb, (idx_t) R.ncols, I{});
+	QrFactors<T> f(Qb, Qc, R);
+	Staged<T> o(view<T>(Out), false, true);
+	qr_reconstruct_dev<T>(o.dev, f.qb.dev, f.qc.dev, f.r.dev);
+	permute_rows<T>(o.dev.t(), perm_bwd); // permute_cols_in_place(out, col_perm.inverse())
 }
 template <typename T, typename I>
 void colpiv_qr_inverse_api(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerSliceRef pf, FaerSliceRef pb)
 {
 	(void) pf;
-	const idx_t n = (idx_t) R.ncols;
-	FH_CHECK((idx_t) pb.len >= n && !is_device_ptr(pb.ptr), "colpiv_qr inverse: perm slices (host memory, ncols entries)");
-	qr_inverse_api<T>(Out, Qb, Qc, R);
-	Staged<T> o(view<T>(Out), true, true);
-	permute_rows_dev_api<T, I>(o.dev, static_cast<const I *>(pb.ptr)); // permute_rows_in_place(out, col_perm.inverse())
+	qr_inverse_check(Out, Qb, Qc, R);
+	DevPerm perm_bwd("colpiv_qr inverse", pb, (idx_t) R.ncols, I{});
+	QrFactors<T> f(Qb, Qc, R);
+	Staged<T> o(view<T>(Out), false, true);
+	qr_inverse_dev<T>(o.dev, f.qb.dev, f.qc.dev, f.r.dev);
+	permute_rows<T>(o.dev, perm_bwd); // permute_rows_in_place(out, col_perm.inverse())
 }
 
 // evd/mod.rs:270-425 behind lib.rs:2385-2399 (U.ncols == 0: no eigenvectors)

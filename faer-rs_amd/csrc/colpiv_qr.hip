@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "perm.h"
 #include "reduce.h"
 #include "xwg.h"
 
@@ -559,8 +560,7 @@ template <typename T> long colpiv_qr_dev(MatV<T> A, MatV<T> H, idx_t *col_perm, 
 		FH_CHECK(hp[(size_t) j] >= 0 && hp[(size_t) j] < n, "colpiv_qr: corrupt permutation");
 		col_perm[j] = hp[(size_t) j];
 	}
-	for (idx_t j = 0; j < n; ++j)
-		col_perm_inv[col_perm[j]] = j;
+	invert_perm(n, col_perm, col_perm_inv);
 	return fin.n_trans;
 }
 template long colpiv_qr_dev<double>(MatV<double>, MatV<double>, idx_t *, idx_t *);

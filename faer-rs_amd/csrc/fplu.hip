@@ -16,6 +16,7 @@
 #include <limits>
 
 #include "common.h"
+#include "perm.h"
 
 namespace fh {
 
@@ -494,14 +495,11 @@ template <typename T> long full_piv_lu_dev(MatV<T> A, idx_t *row_perm, idx_t *ro
 	const idx_t M = A.nrows, N = A.ncols;
 	FH_CHECK(M < (1L << 30) && N < (1L << 30), "full_piv_lu: matrix too large");
 	const idx_t size = M < N ? M : N;
-	for (idx_t i = 0; i < M; ++i)
-		row_perm[i] = i;
-	for (idx_t j = 0; j < N; ++j)
-		col_perm[j] = j;
-	long n_trans = 0;
+	std::vector<int> h((size_t) 2 * size); // the transpositions of the rows, then of the columns, of the view that was factored
+	bool transpose = false;
 	if (size > 0) {
 		auto iabs = [](idx_t v) { return v < 0 ? -v : v; };
-		const bool transpose = !(iabs(A.rs) < iabs(A.cs)); // factor.rs:474-497
+		transpose = !(iabs(A.rs) < iabs(A.cs)); // factor.rs:474-497
 		MatV<T> V = transpose ? A.t() : A;
 		const int m = (int) V.nrows, n = (int) V.ncols;
 		hipStream_t s = ctx().stream;
@@ -551,57 +549,31 @@ template <typename T> long full_piv_lu_dev(MatV<T> A, idx_t *row_perm, idx_t *ro
 			hipLaunchKernelGGL(fplu_finish_kernel<T>, dim3(1024), dim3(256), 0, s, (const T *) S[0], (const T *) S[1], ld, V.p, V.rs, V.cs, m, n,
 					   (const int *) done);
 			FH_HIP(hipGetLastError());
-			std::vector<int> h((size_t) 2 * size);
 			FH_HIP(hipMemcpyAsync(h.data(), rt, (size_t) 2 * size * sizeof(int), hipMemcpyDeviceToHost, s));
 			ctx().sync(); // (also: the scratch copies are released behind their last reader)
-			const int *hrt = h.data(), *hct = h.data() + size;
-			for (idx_t k = 0; k < size; ++k)
-				n_trans += (hrt[k] != k) + (hct[k] != k);
-			const int *row_t = transpose ? hct : hrt, *col_t = transpose ? hrt : hct;
-			for (idx_t i = 0; i < size; ++i) {
-				FH_CHECK(row_t[i] >= 0 && row_t[i] < M && col_t[i] >= 0 && col_t[i] < N, "full_piv_lu: corrupt transposition");
-				std::swap(row_perm[i], row_perm[row_t[i]]);
-				std::swap(col_perm[i], col_perm[col_t[i]]);
+		} else {
+			hipLaunchKernelGGL(fplu_update_kernel<T>, g0, dim3(256), 0, s, V.p, V.rs, V.cs, m, n, 0, 0, 0, 0, partb.as<FpBest>(), done);
+			int nparts = (int) (g0.x * g0.y);
+			const unsigned swap_grid = (unsigned) (((m > n ? m : n) + 255) / 256);
+			for (idx_t k = 0; k < size; ++k) {
+				hipLaunchKernelGGL(fplu_swap_kernel<T>, dim3(swap_grid), dim3(256), 0, s, V.p, V.rs, V.cs, m, n, (int) k, (int) size, transpose ? 1 : 0,
+						   partb.as<const FpBest>(), nparts, rt, ct, done);
+				if (k + 1 == size)
+					break;
+				const dim3 g = grid_of(m - (int) k - 1, n - (int) k - 1);
+				hipLaunchKernelGGL(fplu_update_kernel<T>, g, dim3(256), 0, s, V.p, V.rs, V.cs, m, n, (int) k + 1, (int) k + 1, (int) k, 1,
+						   partb.as<FpBest>(), done);
+				nparts = (int) (g.x * g.y);
 			}
-			for (idx_t i = 0; i < M; ++i)
-				row_perm_inv[row_perm[i]] = i;
-			for (idx_t j = 0; j < N; ++j)
-				col_perm_inv[col_perm[j]] = j;
-			return n_trans;
-		}
-		hipLaunchKernelGGL(fplu_update_kernel<T>, g0, dim3(256), 0, s, V.p, V.rs, V.cs, m, n, 0, 0, 0, 0, partb.as<FpBest>(), done);
-		int nparts = (int) (g0.x * g0.y);
-		const unsigned swap_grid = (unsigned) (((m > n ? m : n) + 255) / 256);
-		for (idx_t k = 0; k < size; ++k) {
-			hipLaunchKernelGGL(fplu_swap_kernel<T>, dim3(swap_grid), dim3(256), 0, s, V.p, V.rs, V.cs, m, n, (int) k, (int) size, transpose ? 1 : 0,
-					   partb.as<const FpBest>(), nparts, rt, ct, done);
-			if (k + 1 == size)
-				break;
-			const dim3 g = grid_of(m - (int) k - 1, n - (int) k - 1);
-			hipLaunchKernelGGL(fplu_update_kernel<T>, g, dim3(256), 0, s, V.p, V.rs, V.cs, m, n, (int) k + 1, (int) k + 1, (int) k, 1,
-					   partb.as<FpBest>(), done);
-			nparts = (int) (g.x * g.y);
-		}
-		FH_HIP(hipGetLastError());
-		std::vector<int> h((size_t) 2 * size);
-		FH_HIP(hipMemcpyAsync(h.data(), rt, (size_t) 2 * size * sizeof(int), hipMemcpyDeviceToHost, s));
-		ctx().sync();
-		const int *hrt = h.data(), *hct = h.data() + size;
-		for (idx_t k = 0; k < size; ++k)
-			n_trans += (hrt[k] != k) + (hct[k] != k);
-		// on the transposed view rows and columns trade places (factor.rs:486-496)
-		const int *row_t = transpose ? hct : hrt, *col_t = transpose ? hrt : hct;
-		for (idx_t i = 0; i < size; ++i) {
-			FH_CHECK(row_t[i] >= 0 && row_t[i] < M && col_t[i] >= 0 && col_t[i] < N, "full_piv_lu: corrupt transposition");
-			std::swap(row_perm[i], row_perm[row_t[i]]);
-			std::swap(col_perm[i], col_perm[col_t[i]]);
+			FH_HIP(hipGetLastError());
+			FH_HIP(hipMemcpyAsync(h.data(), rt, (size_t) 2 * size * sizeof(int), hipMemcpyDeviceToHost, s));
+			ctx().sync();
 		}
 	}
-	for (idx_t i = 0; i < M; ++i)
-		row_perm_inv[row_perm[i]] = i;
-	for (idx_t j = 0; j < N; ++j)
-		col_perm_inv[col_perm[j]] = j;
-	return n_trans;
+	// on the transposed view rows and columns trade places (factor.rs:486-496)
+	const int *row_t = h.data() + (transpose ? size : 0), *col_t = h.data() + (transpose ? 0 : size);
+	return perm_from_transpositions("full_piv_lu", M, size, [&](idx_t i) { return (idx_t) row_t[i]; }, row_perm, row_perm_inv) +
+	       perm_from_transpositions("full_piv_lu", N, size, [&](idx_t j) { return (idx_t) col_t[j]; }, col_perm, col_perm_inv);
 }
 
 template long full_piv_lu_dev<double>(MatV<double>, idx_t *, idx_t *, idx_t *, idx_t *);

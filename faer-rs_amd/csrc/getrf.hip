@@ -34,6 +34,7 @@
 #include <optional>
 
 #include "common.h"
+#include "perm.h"
 #include "lds_blocks.h"
 #include "mfma.h"
 #include "xwg.h"
@@ -1817,10 +1818,8 @@ template <typename T> long getrf_dev(MatV<T> A, idx_t *perm, idx_t *perm_inv)
 	const LuLent lent_rec = t_lu_lent; // consumed by this call whatever happens next
 	t_lu_lent = LuLent{};
 	FH_CHECK(m < (1L << 30) && n < (1L << 30), "partial_piv_lu: matrix too large");
-	for (idx_t i = 0; i < m; ++i)
-		perm[i] = i;
 	const idx_t size = m < n ? m : n;
-	long n_trans = 0;
+	std::vector<int> piv((size_t) size);
 	if (size > 0) {
 		LuWork<T> wk(size, nullptr, nullptr);
 
@@ -1872,7 +1871,6 @@ template <typename T> long getrf_dev(MatV<T> A, idx_t *perm, idx_t *perm_inv)
 		}
 		if (m < n) // factor.rs:278-285 (+ the swaps of the columns right of the square part)
 			LuUpdate<T>{A, 0, size, wk.piv, 0, nullptr}(size, n - size);
-		std::vector<int> piv((size_t) size);
 		int st[4] = {0, 0, 0, 0};
 		FH_HIP(hipMemcpyAsync(piv.data(), wk.piv, (size_t) size * sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
 		FH_HIP(hipMemcpyAsync(st, wk.status, sizeof(st), hipMemcpyDeviceToHost, ctx().stream));
@@ -1885,22 +1883,12 @@ template <typename T> long getrf_dev(MatV<T> A, idx_t *perm, idx_t *perm_inv)
 			// (PartialPivLuStatus::Unknown, faer-ffi/src/lib.rs:591-595) instead of aborting the caller's process.
 			fprintf(stderr, "faer_hip: partial_piv_lu: the cross-workgroup exchange of the panel kernel timed out (GPU shared with other work?)\n");
 			for (idx_t i = 0; i < m; ++i)
-				perm_inv[i] = i;
+				perm[i] = perm_inv[i] = i;
 			return -1;
 		}
-		// factor.rs:274-277: perm = identity with the transpositions applied in order
-		for (idx_t j = 0; j < size; ++j) {
-			const idx_t p = piv[(size_t) j];
-			FH_CHECK(p >= j && p < m, "partial_piv_lu: corrupt pivot index");
-			if (p != j) {
-				std::swap(perm[j], perm[p]);
-				++n_trans;
-			}
-		}
 	}
-	for (idx_t i = 0; i < m; ++i)
-		perm_inv[perm[i]] = i;
-	return n_trans;
+	// factor.rs:274-277: perm = identity with the transpositions applied in order
+	return perm_from_transpositions("partial_piv_lu", m, size, [&](idx_t j) { return (idx_t) piv[(size_t) j]; }, perm, perm_inv);
 }
 
 // `status_dev` (optional, 16 zeroed device ints owned by the caller): the kernels' status words go there and NOTHING is

@@ -15,7 +15,7 @@
 //    kernel on the columns left of the panel, and one read-back of the panel's length (63 or 64).
 //  * Ties of every arg-max go to the lowest index (strict >, rows in ascending order), as in the reference.
 #include "common.h"
-#include "sym_perm.h"
+#include "perm.h"
 
 using namespace fh;
 
@@ -644,22 +644,13 @@ template <typename T> long lblt_dev(MatV<T> A, T *sub, idx_t ss, idx_t *perm, id
 	read_state(st, &n2, ST_N2X2, 1);
 	g_last[2] = (size_t) n2;
 	// factor.rs:1214-1227
-	for (idx_t i = 0; i < n; ++i)
-		perm[i] = i;
-	long count = 0;
-	size_t b = 0;
-	for (idx_t i = 0; i < n; ++i) {
+	size_t b = 0; // the records are relative to the first row of their block
+	auto record = [&](idx_t i) {
 		while (b + 1 < starts.size() && starts[b + 1] <= i)
 			++b;
-		const idx_t p = starts[b] + hp[(size_t) i];
-		FH_CHECK(p >= i && p < n, "lblt: pivot record out of range");
-		if (p != i)
-			++count;
-		std::swap(perm[i], perm[p]);
-	}
-	for (idx_t i = 0; i < n; ++i)
-		perm_inv[perm[i]] = i;
-	return count;
+		return starts[b] + (idx_t) hp[(size_t) i];
+	};
+	return perm_from_transpositions("lblt", n, n, record, perm, perm_inv);
 }
 
 // ------------------------------------------------------------------------------------------------ solve / reconstruct
@@ -721,8 +712,6 @@ FaerLbltStatus factor_api(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut pf, Fae
 	const idx_t n = (idx_t) A.nrows;
 	FH_CHECK(A.nrows == A.ncols, "lblt: matrix must be square");
 	FH_CHECK((idx_t) subdiag.len == n, "lblt: subdiag must have dim entries");
-	FH_CHECK((idx_t) pf.len == n && (idx_t) pb.len == n, "lblt: perm slices must have dim entries");
-	FH_CHECK(n == 0 || (!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr)), "lblt: perm slices must be host memory");
 	const int p = (int) params.pivoting;
 	if (p < (int) FaerPivotingStrategy_Partial || p >= (int) FaerPivotingStrategy_Full) {
 		fprintf(stderr, "faer_hip: fatal: lblt_factor_in_place: pivoting strategy %s (%d) is not implemented (Partial, PartialDiag, Rook, RookDiag only)\n",
@@ -739,11 +728,7 @@ FaerLbltStatus factor_api(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut pf, Fae
 		Staged<T> sd(vview<T>(subdiag), false, true);
 		nt = lblt_dev<T>(a.dev, sd.dev.p, sd.dev.rs, perm.data(), perm_inv.data(), rook, diagonal);
 	}
-	I *f = static_cast<I *>(pf.ptr), *b = static_cast<I *>(pb.ptr);
-	for (idx_t i = 0; i < n; ++i) {
-		f[i] = (I) perm[(size_t) i];
-		b[i] = (I) perm_inv[(size_t) i];
-	}
+	store_perm<I>("lblt", pf, pb, perm.data(), perm_inv.data(), n);
 	FaerLbltStatus stt;
 	memset(&stt, 0, sizeof(stt));
 	stt.tag = FaerLbltStatus_Ok;
@@ -752,31 +737,30 @@ FaerLbltStatus factor_api(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut pf, Fae
 }
 
 // solve.rs:35-104
-template <typename T, typename I>
-void solve_dev(MatV<const T> L, MatV<const T> d, MatV<const T> sd, const void *pf, const void *pb, MatV<T> X)
+template <typename T> void solve_dev(MatV<const T> L, MatV<const T> d, MatV<const T> sd, const DevPerm &pf, const DevPerm &pb, MatV<T> X)
 {
 	const idx_t n = L.nrows, k = X.ncols;
 	if (n == 0 || k == 0)
 		return;
-	permute_rows<T, I>(X, pf);
+	permute_rows<T>(X, pf);
 	trsm_lower_dev<T>(L, true, X);
 	hipLaunchKernelGGL(lblt_block_diag_solve_kernel<T>, dim3((unsigned) ((n + 255) / 256), (unsigned) k), dim3(256), 0, ctx().stream, X.p, X.rs,
 			   X.cs, n, k, d.p, d.rs, sd.p, sd.rs);
 	FH_HIP(hipGetLastError());
 	trsm_upper_dev<T>(L.t(), true, X);
-	permute_rows<T, I>(X, pb);
+	permute_rows<T>(X, pb);
 }
 
 template <typename T, typename I>
 void solve_api(FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs)
 {
 	const size_t n = L.nrows;
-	FH_CHECK(L.ncols == n && rhs.nrows == n && diag.len == n && subdiag.len == n && pf.len >= n && pb.len >= n, "lblt solve: dimension mismatch");
+	FH_CHECK(L.ncols == n && rhs.nrows == n && diag.len == n && subdiag.len == n, "lblt solve: dimension mismatch");
 	FH_CHECK(rhs.ncols < 65536, "lblt solve: too many right-hand sides");
-	FH_CHECK(n == 0 || (!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr)), "lblt solve: perm slices must be host memory");
+	DevPerm fwd("lblt solve", pf, (idx_t) n, I{}), bwd("lblt solve", pb, (idx_t) n, I{});
 	Staged<const T> l(view<T>(L), true, false), d(vview<T>(diag), true, false), sd(vview<T>(subdiag), true, false);
 	Staged<T> x(view<T>(rhs), true, true);
-	solve_dev<T, I>(l.dev, d.dev, sd.dev, pf.ptr, pb.ptr, x.dev);
+	solve_dev<T>(l.dev, d.dev, sd.dev, fwd, bwd, x.dev);
 }
 
 // reconstruct.rs:12-87 (the lower triangle of out only)
@@ -784,16 +768,16 @@ template <typename T, typename I>
 void reconstruct_api(FaerMatMut Out, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef pf, FaerSliceRef pb)
 {
 	const idx_t n = (idx_t) L.nrows;
-	FH_CHECK((idx_t) L.ncols == n && (idx_t) Out.nrows == n && (idx_t) Out.ncols == n && (idx_t) diag.len == n && (idx_t) subdiag.len == n &&
-			 (idx_t) pf.len >= n && (idx_t) pb.len >= n,
+	FH_CHECK((idx_t) L.ncols == n && (idx_t) Out.nrows == n && (idx_t) Out.ncols == n && (idx_t) diag.len == n && (idx_t) subdiag.len == n,
 		 "lblt reconstruct: dimension mismatch");
 	FH_CHECK(n < 65536, "lblt reconstruct: dimension too large");
+	check_perm_slice("lblt reconstruct", pf, n);
+	DevPerm bwd("lblt reconstruct", pb, n, I{});
 	if (n == 0)
 		return;
-	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "lblt reconstruct: perm slices must be host memory");
 	Staged<const T> l(view<T>(L), true, false), d(vview<T>(diag), true, false), sd(vview<T>(subdiag), true, false);
 	Staged<T> o(view<T>(Out), true, true); // the strict upper triangle is kept
-	Scratch xb((size_t) n * (size_t) n * sizeof(T) + 256), tb((size_t) n * (size_t) n * sizeof(T) + 256), pbuf((size_t) n * sizeof(idx_t));
+	Scratch xb((size_t) n * (size_t) n * sizeof(T) + 256), tb((size_t) n * (size_t) n * sizeof(T) + 256);
 	MatV<T> X{xb.as<T>(), n, n, 1, n}, tmp{tb.as<T>(), n, n, 1, n};
 	const dim3 grid((unsigned) ((n + 255) / 256), (unsigned) n);
 	hipLaunchKernelGGL(lblt_scale_kernel<T>, grid, dim3(256), 0, ctx().stream, X.p, n, l.dev.p, l.dev.rs, l.dev.cs, d.dev.p, d.dev.rs, sd.dev.p,
@@ -801,9 +785,7 @@ void reconstruct_api(FaerMatMut Out, FaerMatRef L, FaerVecRef diag, FaerVecRef s
 	FH_HIP(hipGetLastError());
 	matmul_triangular_dev<T>(tmp, (int) FaerBlock_TriangularLower, false, l.dev, (int) FaerBlock_UnitTriangularLower, X.t().c(),
 				 (int) FaerBlock_Rectangular, (T) 1);
-	upload_perm<I>(pbuf, pb.ptr, n);
-	hipLaunchKernelGGL(lblt_sym_gather_kernel<T>, grid, dim3(256), 0, ctx().stream, o.dev.p, o.dev.rs, o.dev.cs, n, tmp.p, pbuf.as<idx_t>());
-	FH_HIP(hipGetLastError());
+	sym_gather<T>(o.dev, tmp.p, bwd);
 	ctx().sync();
 }
 
@@ -812,19 +794,17 @@ template <typename T, typename I>
 void inverse_api(FaerMatMut Out, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef pf, FaerSliceRef pb)
 {
 	const size_t n = L.nrows;
-	FH_CHECK(L.ncols == n && Out.nrows == n && Out.ncols == n && diag.len == n && subdiag.len == n && pf.len >= n && pb.len >= n,
-		 "lblt inverse: dimension mismatch");
+	FH_CHECK(L.ncols == n && Out.nrows == n && Out.ncols == n && diag.len == n && subdiag.len == n, "lblt inverse: dimension mismatch");
 	FH_CHECK(n < 65536, "lblt inverse: dimension too large");
+	DevPerm fwd("lblt inverse", pf, (idx_t) n, I{}), bwd("lblt inverse", pb, (idx_t) n, I{});
 	if (n == 0)
 		return;
-	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "lblt inverse: perm slices must be host memory");
 	Staged<const T> l(view<T>(L), true, false), d(vview<T>(diag), true, false), sd(vview<T>(subdiag), true, false);
 	Staged<T> o(view<T>(Out), false, true);
 	svd_identity_dev<T>(o.dev);
-	solve_dev<T, I>(l.dev, d.dev, sd.dev, pf.ptr, pb.ptr, o.dev);
+	solve_dev<T>(l.dev, d.dev, sd.dev, fwd, bwd, o.dev);
 }
 
-FaerLayout lay(size_t bytes) { return FaerLayout{bytes, 64}; }
 size_t up64(size_t b) { return (b + 63) / 64 * 64; }
 
 } // namespace
@@ -850,7 +830,7 @@ X(f32, float)
 		size_t bs = params.block_size; /* factor.rs:1128-1140 */                                                                           \
 		if (bs < 2 || dim <= bs)                                                                                                           \
 			bs = 0;                                                                                                                    \
-		return lay(dim == 0 ? 0 : up64(dim * sizeof(size_t)) + dim * bs * sizeof(T));                                                     \
+		return layout(dim == 0 ? 0 : up64(dim * sizeof(size_t)) + dim * bs * sizeof(T), 64);                                                 \
 	}                                                                                                                                          \
 	FaerLbltStatus libfaer_v0_23_lblt_factor_in_place_##it##_##suf(FaerMatMut A, FaerVecMut subdiag, FaerSliceMut perm_fwd,                    \
 								       FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerLbltParams params) \
@@ -862,7 +842,7 @@ X(f32, float)
 	FaerLayout libfaer_v0_23_lblt_solve_in_place_scratch_##it##_##suf(size_t dim, size_t rhs_ncols, FaerPar par)                               \
 	{                                                                                                                                          \
 		(void) par;                                                                                                                        \
-		return lay(dim * rhs_ncols * sizeof(T)); /* solve.rs:11-18 */                                                                      \
+		return layout(dim * rhs_ncols * sizeof(T), 64); /* solve.rs:11-18 */                                                                  \
 	}                                                                                                                                          \
 	void libfaer_v0_23_lblt_solve_in_place_##it##_##suf(FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerConj A_conj,                    \
 							    FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par,             \
@@ -876,7 +856,7 @@ X(f32, float)
 	FaerLayout libfaer_v0_23_lblt_reconstruct_scratch_##it##_##suf(size_t dim, FaerPar par)                                                    \
 	{                                                                                                                                          \
 		(void) par;                                                                                                                        \
-		return lay(dim * dim * sizeof(T)); /* reconstruct.rs:4-10 */                                                                       \
+		return layout(dim * dim * sizeof(T), 64); /* reconstruct.rs:4-10 */                                                                   \
 	}                                                                                                                                          \
 	void libfaer_v0_23_lblt_reconstruct_##it##_##suf(FaerMatMut A, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd,   \
 							 FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem)                                     \
@@ -888,7 +868,7 @@ X(f32, float)
 	FaerLayout libfaer_v0_23_lblt_inverse_scratch_##it##_##suf(size_t dim, FaerPar par)                                                        \
 	{                                                                                                                                          \
 		(void) par;                                                                                                                        \
-		return lay(dim * dim * sizeof(T)); /* inverse.rs:3-9 */                                                                            \
+		return layout(dim * dim * sizeof(T), 64); /* inverse.rs:3-9 */                                                                        \
 	}                                                                                                                                          \
 	void libfaer_v0_23_lblt_inverse_##it##_##suf(FaerMatMut A_inv, FaerMatRef L, FaerVecRef diag, FaerVecRef subdiag, FaerSliceRef perm_fwd,   \
 						     FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem)                                         \

@@ -15,7 +15,7 @@
 //  * piv_llt_leaf_kernel, one workgroup: the last <= PL_NB rows as a full symmetric image in LDS, unblocked and eagerly updated.
 //  * Ties of every arg-max go to the lowest index (strict >, candidates combined in ascending row order), as in the reference.
 #include "common.h"
-#include "sym_perm.h"
+#include "perm.h"
 #include <limits>
 
 using namespace fh;
@@ -399,17 +399,7 @@ template <typename T> PivLltResult piv_llt_dev(MatV<T> A, idx_t *perm, idx_t *pe
 	ctx().sync();
 	g_last[2] = (size_t) res.rank;
 	// factor.rs:63-65, :127, :153, :187-189
-	for (idx_t i = 0; i < n; ++i)
-		perm[i] = i;
-	for (idx_t j = 0; j < res.rank; ++j) {
-		const idx_t p = hp[(size_t) j];
-		FH_CHECK(p >= j && p < n, "piv_llt: pivot record out of range");
-		if (p != j)
-			++res.count;
-		std::swap(perm[j], perm[p]);
-	}
-	for (idx_t i = 0; i < n; ++i)
-		perm_inv[perm[i]] = i;
+	res.count = perm_from_transpositions("piv_llt", n, res.rank, [&](idx_t j) { return (idx_t) hp[(size_t) j]; }, perm, perm_inv);
 	return res;
 }
 
@@ -417,8 +407,6 @@ template <typename T, typename I> FaerPivLltStatus factor_api(FaerMatMut A, Faer
 {
 	const idx_t n = (idx_t) A.nrows;
 	FH_CHECK(A.nrows == A.ncols, "piv_llt: matrix must be square");
-	FH_CHECK((idx_t) pf.len == n && (idx_t) pb.len == n, "piv_llt: perm slices must have dim entries");
-	FH_CHECK(n == 0 || (!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr)), "piv_llt: perm slices must be host memory");
 	std::vector<idx_t> perm((size_t) n), perm_inv((size_t) n);
 	PivLltResult r;
 	{
@@ -432,11 +420,7 @@ template <typename T, typename I> FaerPivLltStatus factor_api(FaerMatMut A, Faer
 		stt.non_positive_pivot.index = (size_t) r.index;
 		return stt;
 	}
-	I *f = static_cast<I *>(pf.ptr), *b = static_cast<I *>(pb.ptr);
-	for (idx_t i = 0; i < n; ++i) {
-		f[i] = (I) perm[(size_t) i];
-		b[i] = (I) perm_inv[(size_t) i];
-	}
+	store_perm<I>("piv_llt", pf, pb, perm.data(), perm_inv.data(), n);
 	stt.tag = FaerPivLltStatus_Ok;
 	stt.ok.rank = (size_t) r.rank;
 	stt.ok.transposition_count = (size_t) r.count;
@@ -447,41 +431,29 @@ template <typename T, typename I> FaerPivLltStatus factor_api(FaerMatMut A, Faer
 template <typename T, typename I> void solve_api(FaerMatRef L, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs)
 {
 	const size_t n = L.nrows;
-	FH_CHECK(L.ncols == n && rhs.nrows == n && pf.len >= n && pb.len >= n, "piv_llt solve: dimension mismatch");
+	FH_CHECK(L.ncols == n && rhs.nrows == n, "piv_llt solve: dimension mismatch");
 	FH_CHECK(rhs.ncols < 65536, "piv_llt solve: too many right-hand sides");
+	DevPerm fwd("piv_llt solve", pf, (idx_t) n, I{}), bwd("piv_llt solve", pb, (idx_t) n, I{});
 	if (n == 0 || rhs.ncols == 0)
 		return;
-	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "piv_llt solve: perm slices must be host memory");
 	Staged<const T> l(view<T>(L), true, false);
 	Staged<T> x(view<T>(rhs), true, true);
-	permute_rows<T, I>(x.dev, pf.ptr);
+	permute_rows<T>(x.dev, fwd);
 	trsm_lower_dev<T>(l.dev, false, x.dev);
 	trsm_upper_dev<T>(l.dev.t(), false, x.dev);
-	permute_rows<T, I>(x.dev, pb.ptr);
-}
-
-// lower(out)[i, j] = tmp[perm_bwd ...] (reconstruct.rs:40-51, inverse.rs:42-53); tmp: n x n column major, lower triangle
-template <typename T, typename I> void sym_gather(MatV<T> out, const T *tmp, const void *pb_host)
-{
-	const idx_t n = out.nrows;
-	Scratch pbuf((size_t) n * sizeof(idx_t));
-	upload_perm<I>(pbuf, pb_host, n);
-	hipLaunchKernelGGL(lblt_sym_gather_kernel<T>, dim3((unsigned) ((n + 255) / 256), (unsigned) n), dim3(256), 0, ctx().stream, out.p, out.rs,
-			   out.cs, n, tmp, pbuf.as<idx_t>());
-	FH_HIP(hipGetLastError());
-	ctx().sync();
+	permute_rows<T>(x.dev, bwd);
 }
 
 // reconstruct.rs:12-52 / inverse.rs:12-54 (the lower triangle of out only)
 template <typename T, typename I> void rebuild_api(FaerMatMut Out, FaerMatRef L, FaerSliceRef pf, FaerSliceRef pb, bool inverse)
 {
 	const idx_t n = (idx_t) L.nrows;
-	FH_CHECK((idx_t) L.ncols == n && (idx_t) Out.nrows == n && (idx_t) Out.ncols == n && (idx_t) pf.len >= n && (idx_t) pb.len >= n,
-		 "piv_llt reconstruct / inverse: dimension mismatch");
+	FH_CHECK((idx_t) L.ncols == n && (idx_t) Out.nrows == n && (idx_t) Out.ncols == n, "piv_llt reconstruct / inverse: dimension mismatch");
 	FH_CHECK(n < 65536, "piv_llt reconstruct / inverse: dimension too large");
+	check_perm_slice("piv_llt reconstruct / inverse", pf, n);
+	DevPerm bwd("piv_llt reconstruct / inverse", pb, n, I{});
 	if (n == 0)
 		return;
-	FH_CHECK(!is_device_ptr(pf.ptr) && !is_device_ptr(pb.ptr), "piv_llt reconstruct / inverse: perm slices must be host memory");
 	Staged<const T> l(view<T>(L), true, false);
 	Staged<T> o(view<T>(Out), true, true); // the strict upper triangle is kept
 	Scratch tb((size_t) n * (size_t) n * sizeof(T) + 256);
@@ -496,10 +468,9 @@ template <typename T, typename I> void rebuild_api(FaerMatMut Out, FaerMatRef L,
 		matmul_triangular_dev<T>(tmp, (int) FaerBlock_TriangularLower, false, W.t().c(), (int) FaerBlock_TriangularUpper, W.c(),
 					 (int) FaerBlock_TriangularLower, (T) 1);
 	}
-	sym_gather<T, I>(o.dev, tmp.p, pb.ptr);
+	sym_gather<T>(o.dev, tmp.p, bwd); // reconstruct.rs:40-51, inverse.rs:42-53
+	ctx().sync();
 }
-
-FaerLayout lay(size_t bytes) { return FaerLayout{bytes, 64}; }
 
 } // namespace
 
@@ -522,7 +493,7 @@ X(f32, float)
 	{                                                                                                                                          \
 		(void) par;                                                                                                                        \
 		(void) params;                                                                                                                     \
-		return lay(2 * dim * sizeof(T)); /* factor.rs:37-45 */                                                                             \
+		return layout(2 * dim * sizeof(T), 64); /* factor.rs:37-45 */                                                                         \
 	}                                                                                                                                          \
 	FaerPivLltStatus libfaer_v0_23_piv_llt_factor_in_place_##it##_##suf(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd,            \
 									    FaerPar par, FaerMemAlloc mem, FaerPivLltParams params)                \
@@ -535,7 +506,7 @@ X(f32, float)
 	FaerLayout libfaer_v0_23_piv_llt_solve_in_place_scratch_##it##_##suf(size_t dim, size_t rhs_ncols, FaerPar par)                            \
 	{                                                                                                                                          \
 		(void) par;                                                                                                                        \
-		return lay(dim * rhs_ncols * sizeof(T)); /* solve.rs:4-11 */                                                                       \
+		return layout(dim * rhs_ncols * sizeof(T), 64); /* solve.rs:4-11 */                                                                   \
 	}                                                                                                                                          \
 	void libfaer_v0_23_piv_llt_solve_in_place_##it##_##suf(FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerConj A_conj,        \
 							       FaerMatMut rhs, FaerPar par, FaerMemAlloc mem)                                      \
@@ -548,7 +519,7 @@ X(f32, float)
 	FaerLayout libfaer_v0_23_piv_llt_reconstruct_scratch_##it##_##suf(size_t dim, FaerPar par)                                                 \
 	{                                                                                                                                          \
 		(void) par;                                                                                                                        \
-		return lay(dim * dim * sizeof(T)); /* reconstruct.rs:4-10 */                                                                       \
+		return layout(dim * dim * sizeof(T), 64); /* reconstruct.rs:4-10 */                                                                   \
 	}                                                                                                                                          \
 	void libfaer_v0_23_piv_llt_reconstruct_##it##_##suf(FaerMatMut A, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, \
 							    FaerMemAlloc mem)                                                                      \
@@ -560,7 +531,7 @@ X(f32, float)
 	FaerLayout libfaer_v0_23_piv_llt_inverse_scratch_##it##_##suf(size_t dim, FaerPar par)                                                     \
 	{                                                                                                                                          \
 		(void) par;                                                                                                                        \
-		return lay(dim * dim * sizeof(T)); /* inverse.rs:4-10 */                                                                           \
+		return layout(dim * dim * sizeof(T), 64); /* inverse.rs:4-10 */                                                                       \
 	}                                                                                                                                          \
 	void libfaer_v0_23_piv_llt_inverse_##it##_##suf(FaerMatMut A_inv, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, \
 							FaerMemAlloc mem)                                                                          \
