@@ -1117,6 +1117,19 @@ def debug_piv_llt_last():
     return tuple(int(v) for v in out)
 
 
+def debug_scratch_fill(byte=-1):
+    """tests: from now on every device scratch buffer the library hands to itself is first filled, over its whole pool size, with
+    `byte` (0 .. 255); -1 switches the fill off again (the default).  Process wide; resets debug_scratch_fill_stats."""
+    lib().faer_hip_debug_scratch_fill(C.c_int(int(byte)))
+
+
+def debug_scratch_fill_stats():
+    """(fills, bytes filled) since the last debug_scratch_fill"""
+    out = (C.c_size_t * 2)()
+    lib().faer_hip_debug_scratch_fill_stats(out)
+    return int(out[0]), int(out[1])
+
+
 # ------------------------------------------------------------------ high level owners (faer/src/linalg/solvers.rs)
 def _empty_like_f(a, shape):
     if _is_torch(a):

@@ -176,7 +176,9 @@ template <typename T> FaerQrStatus qr_api(FaerMatMut A, FaerMatMut Q, FaerQrPara
 	long rank;
 	{
 		Staged<T> a(view<T>(A), true, true);
-		Staged<T> q(view<T>(Q), false, true);
+		// (copied in: the factorization writes the upper triangles of Q_coeff's diagonal blocks only, the rest keeps the caller's values
+		// as it does for a device operand -- staged without copy-in, stale scratch bytes went back to the host in those cells)
+		Staged<T> q(view<T>(Q), true, true);
 		rank = geqrf_dev<T>(a.dev, q.dev, (idx_t) params.blocking_threshold);
 	}
 	FaerQrStatus st;
@@ -514,7 +516,9 @@ template <typename T, typename I> FaerColPivQrStatus colpiv_qr_api(FaerMatMut A,
 	long nt;
 	{
 		Staged<T> a(view<T>(A), true, true);
-		Staged<T> q(view<T>(Q), false, true);
+		// (copied in: the factorization writes the upper triangles of Q_coeff's diagonal blocks only, the rest keeps the caller's values
+		// as it does for a device operand -- staged without copy-in, stale scratch bytes went back to the host in those cells)
+		Staged<T> q(view<T>(Q), true, true);
 		nt = colpiv_qr_dev<T>(a.dev, q.dev, cp.data(), cpi.data());
 	}
 	store_perm<I>("colpiv_qr", pf, pb, cp.data(), cpi.data(), n);
@@ -1506,6 +1510,8 @@ void faer_hip_debug_qr_panels_one_pass(int on) { tsqr_debug_panels(on); }
 void faer_hip_debug_qr_one_pass_shape_rule(long min_rows, long min_rows_per_column) { tsqr_debug_shape_rule(min_rows, min_rows_per_column); }
 void faer_hip_debug_fplu_inplace(int on) { fplu_debug_inplace(on); }
 void faer_hip_debug_level2_force_memory_bodies(int on) { level2_debug_force_memory_bodies(on); }
+void faer_hip_debug_scratch_fill(int byte_or_minus_one) { debug_scratch_fill(byte_or_minus_one); }
+void faer_hip_debug_scratch_fill_stats(size_t out[2]) { debug_scratch_fill_stats(out); }
 void *faer_hip_debug_internal_stream(int which)
 {
 	Ctx &c = ctx();

@@ -138,6 +138,8 @@ template <auto Kernel> inline void raise_dynamic_lds(size_t bytes)
 void debug_stream_xcc(int which, int nblocks, unsigned *out_host); // which: 0 caller's stream, 1 bulk, 2 panel
 void prof_collect(double *out, double *spans = nullptr, size_t cap = 0, size_t *nspans = nullptr); // Ctx::PROF_CLASSES x {ms, launches, units} of the spans recorded since prof_on; optionally one record of 8 doubles per span (ctx.hip)
 double xwg_hop_us(int iters); // idle-chip hand-off latency between two workgroups, microseconds (ctx.hip)
+void debug_scratch_fill(int byte_or_minus_one); // debug: every scratch buffer handed out is filled with this byte first (-1 = off, the default; ctx.hip)
+void debug_scratch_fill_stats(size_t out[2]);  // {fills, bytes filled} since the last debug_scratch_fill
 void ctx_shutdown(); // releases the calling thread's look-ahead streams / events; safe without a device
 
 // stream `s` waits for event `e`

@@ -303,6 +303,36 @@ hipEvent_t Ctx::next_event()
 	return la_events[la_next_event++];
 }
 
+// Debug scratch fill (faer_hip_debug_scratch_fill): process wide, off (-1) by default.  While on, every buffer alloc() hands
+// out is filled over its whole pool size with one byte, on the stream recorded as its owner -- the ordering the pool promises
+// for the previous user's last write, so the fill stands for "stale contents of the previous user" and nothing stronger.
+static std::atomic<int> g_scratch_fill{-1};
+static std::atomic<unsigned long long> g_scratch_fills{0}, g_scratch_fill_bytes{0};
+
+void debug_scratch_fill(int byte_or_minus_one)
+{
+	g_scratch_fill.store(byte_or_minus_one < 0 ? -1 : (byte_or_minus_one & 0xff), std::memory_order_relaxed);
+	g_scratch_fills.store(0, std::memory_order_relaxed);
+	g_scratch_fill_bytes.store(0, std::memory_order_relaxed);
+}
+
+void debug_scratch_fill_stats(size_t out[2])
+{
+	out[0] = (size_t) g_scratch_fills.load(std::memory_order_relaxed);
+	out[1] = (size_t) g_scratch_fill_bytes.load(std::memory_order_relaxed);
+}
+
+static void *scratch_hand_out(const Ctx::Buf &b)
+{
+	const int fill = g_scratch_fill.load(std::memory_order_relaxed);
+	if (__builtin_expect(fill >= 0, 0)) {
+		FH_HIP(hipMemsetAsync(b.p, fill, b.bytes, b.owner));
+		g_scratch_fills.fetch_add(1, std::memory_order_relaxed);
+		g_scratch_fill_bytes.fetch_add(b.bytes, std::memory_order_relaxed);
+	}
+	return b.p;
+}
+
 void *Ctx::alloc(size_t bytes)
 {
 	if (bytes == 0)
@@ -318,7 +348,7 @@ void *Ctx::alloc(size_t bytes)
 	if (best >= 0 && pool[best].bytes <= 2 * bytes + (1 << 20)) {
 		pool[best].used = true;
 		pool[best].owner = stream;
-		return pool[best].p;
+		return scratch_hand_out(pool[best]);
 	}
 	// No buffer free on THIS stream.  Free buffers last used on OTHER streams become reusable once that work has
 	// finished: poll (never wait) before growing the pool, so that a caller that changes streams
@@ -357,7 +387,7 @@ void *Ctx::alloc(size_t bytes)
 			if (best >= 0 && pool[best].bytes <= 2 * bytes + (1 << 20)) {
 				pool[best].used = true;
 				pool[best].owner = stream;
-				return pool[best].p;
+				return scratch_hand_out(pool[best]);
 			}
 		}
 	}
@@ -376,7 +406,7 @@ void *Ctx::alloc(size_t bytes)
 		FH_HIP(hipMalloc(&p, bytes));
 	}
 	pool.push_back(Buf{p, bytes, true, stream});
-	return p;
+	return scratch_hand_out(pool.back());
 }
 
 // the caller moves to another stream: its free buffers can be handed to any stream as soon as the old stream is idle

@@ -747,6 +747,14 @@ FAER_HIP_API void faer_hip_debug_fplu_inplace(int on);
 /* tests: 1 = the single-workgroup vector kernels of the tridiagonal / bidiagonal / Hessenberg reductions run their memory-resident bodies
  * at every size (default: from 4096 remaining rows down they keep their columns in registers); results must not depend on it. */
 FAER_HIP_API void faer_hip_debug_level2_force_memory_bodies(int on);
+/* tests: scratch poisoning.  `byte_or_minus_one` in 0 .. 255: from now on every device scratch buffer the library hands to itself (the
+ * pool behind every internal workspace and every staged host operand, all threads) is first filled, over the whole pool buffer and not
+ * only the requested size, with that byte, stream ordered like the previous user's last write; -1 (the default) switches it off.  Results
+ * must not depend on it: a kernel that reads scratch nothing in the same call has written shows as NaNs (0xFF) or as a difference
+ * between two fill bytes (tests/test_gpu_scratch_poison.py).  faer_hip_debug_scratch_fill_stats: out = {fills, bytes filled} since the
+ * last faer_hip_debug_scratch_fill. */
+FAER_HIP_API void faer_hip_debug_scratch_fill(int byte_or_minus_one);
+FAER_HIP_API void faer_hip_debug_scratch_fill_stats(size_t out[2]);
 /* host logic of the distributed LU: may a step factor its look-ahead panel of `panel_rows` rows on the CU-masked panel stream? */
 FAER_HIP_API int faer_hip_debug_dist_two_streams_ok(size_t panel_rows, FaerHipDType dtype, int panel_cus, int all_cus);
 /* Instrumented builds (make -C csrc timing): prints and resets the in-kernel phase counters; a no-op otherwise. */
