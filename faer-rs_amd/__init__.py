@@ -351,6 +351,29 @@ def gemm(dst, dst_kind, accum, lhs, rhs, alpha=1.0, row_idx=None, col_idx=None, 
     return dst
 
 
+GEMM_PLAN_INPUTS = ("m", "n", "k", "elem_bytes", "kind", "add", "alpha_sign", "drs", "dcs", "ars", "acs", "brs", "bcs", "indexed", "diag",
+                    "a_struct", "b_struct", "k_trim", "tri_skip", "stair_nb", "stair_gap", "stair_row0", "prefer_big_tiles", "variant")
+GEMM_PLAN_FIELDS = ("transposed", "tile", "tri_skip_split", "akm", "bkm", "bm", "bn", "ntm", "ntn", "tri_enum", "tri_off", "splits",
+                    "k_per_split", "fast_io", "prof_class", "routes")
+GEMM_TILES = ("Extra64", "Pipe64", "Pipe128", "PipeWide", "Legacy64", "Legacy128")
+
+
+def debug_gemm_plan(**problem):
+    """faer_hip_debug_gemm_plan (no GPU needed): the dense dispatch's plan for a product given as GEMM_PLAN_INPUTS (m, n, k and
+    elem_bytes are required, strides default to column-major operands, everything else to 0) -> dict of GEMM_PLAN_FIELDS, or the
+    refusal message as a str, or None if it is not a dense product"""
+    q = dict(drs=1, dcs=problem["m"], ars=1, acs=problem["m"], brs=1, bcs=problem["k"])
+    q.update(problem)
+    assert set(q) <= set(GEMM_PLAN_INPUTS), set(q) - set(GEMM_PLAN_INPUTS)
+    inp = (C.c_longlong * len(GEMM_PLAN_INPUTS))(*(int(q.get(f, 0)) for f in GEMM_PLAN_INPUTS))
+    out = (C.c_int * len(GEMM_PLAN_FIELDS))()
+    why = C.c_char_p()
+    rc = lib().faer_hip_debug_gemm_plan(inp, out, C.byref(why))
+    if rc == 0:
+        return dict(zip(GEMM_PLAN_FIELDS, out))
+    return why.value.decode() if rc == 1 else None
+
+
 def _trsm(name, t, rhs, par):
     suf, _, _ = _dtype_suffix(rhs)
     getattr(lib(), f"libfaer_v0_23_{name}_{suf}")(_mat(t), C.c_int(CONJ_NO), _mat(rhs, MatMut), par)

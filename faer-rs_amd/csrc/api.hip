@@ -1416,6 +1416,31 @@ size_t faer_hip_debug_llt_steps(size_t n, size_t la_min, size_t tail_rows, size_
 {
 	return llt_debug_steps((idx_t) n, (idx_t) la_min, (idx_t) tail_rows, (idx_t) side_rmin, (idx_t) dpanel_rmin, codes, cap);
 }
+int faer_hip_debug_gemm_plan(const long long q[24], int out[16], const char **refusal)
+{
+	if (refusal)
+		*refusal = nullptr;
+	for (int i = 0; i < 3; ++i)
+		if (q[i] < 1 || q[i] >= (1LL << 31))
+			return -1;
+	if ((q[3] != 4 && q[3] != 8) || q[4] < 0 || q[4] > 2 || q[15] < 0 || q[15] > 6 || q[16] < 0 || q[16] > 6 || q[17] < 0 || q[17] > 2)
+		return -1;
+	GemmProblem p{(idx_t) q[0], (idx_t) q[1], (idx_t) q[2], (int) q[3], (DstKind) q[4], q[5] != 0, (int) q[6], (idx_t) q[7], (idx_t) q[8],
+		      (idx_t) q[9], (idx_t) q[10], (idx_t) q[11], (idx_t) q[12], q[13] != 0, q[14] != 0, (int) q[15], (int) q[16], (int) q[17],
+		      (idx_t) q[18], (idx_t) q[19], (idx_t) q[20], (idx_t) q[21], q[22] != 0, (int) q[23], false};
+	gemm_orient(p);
+	GemmPlan g;
+	const char *why = gemm_plan(p, g);
+	if (why) {
+		if (refusal)
+			*refusal = why;
+		return 1;
+	}
+	const int v[16] = {g.transposed, (int) g.tile, g.tri_skip_split, g.akm, g.bkm, g.bm, g.bn, g.ntm, g.ntn, g.tri_enum, g.tri_off, g.splits,
+			   g.k_per_split, g.fast_io, g.prof_class, (int) g.routes};
+	memcpy(out, v, sizeof(v));
+	return 0;
+}
 void faer_hip_debug_dump_timing(void)
 {
 	trsm_dump_timing();

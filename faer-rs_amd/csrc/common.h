@@ -319,10 +319,6 @@ template <typename T> struct GemmExtra {
 	idx_t diag_stride = 0;
 	int a_struct = 0, b_struct = 0; // FaerBlock codes of the operands (triangular products)
 	bool dst_strict = false;	// with DST_LOWER / DST_UPPER: leave the diagonal untouched
-	// in-place product dst = alpha * A * B with dst aliasing an operand whose other factor is a square
-	// K x K (K <= 128) matrix: 1 = B aliases dst (dst = S * dst), 2 = A aliases dst (dst = dst * S).
-	// (The value refers to the operands as passed; gemm_dev swaps it when it transposes the problem.)
-	int inplace = 0;
 	// dense-kernel shortcuts for the factorization drivers (plain products only):
 	//   k_trim 1: rhs(k, n) is zero for k > n (upper triangular rhs with an explicitly zeroed lower part), 2: lhs(m, k)
 	//   is zero for k > m -- each tile stops its K loop at the end of its diagonal block instead of multiplying zeros;
@@ -339,6 +335,58 @@ template <typename T> struct GemmExtra {
 	// tiles with more K slices instead of the 64 x 64 tiles the tile-count rule picks (square QR N = 8192: -3 %, tools/gpu_qr_square_gemm_ab.py)
 	bool prefer_big_tiles = false;
 };
+
+// Ctx::gemm_variant (faer_hip_set_gemm_variant): the integers are public, tools and tests pass them through
+enum GemmVariant {
+	GEMM_VARIANT_AUTO = 0,	      // the rules of gemm_plan
+	GEMM_VARIANT_FORCE_128 = 1,   // pipelined 128 x 128 tile
+	GEMM_VARIANT_FORCE_64 = 2,    // pipelined 64 x 64 tile
+	GEMM_VARIANT_FORCE_WIDE = 3,  // pipelined 128 x 256 tile wherever it can run (plain full and square lower products)
+	GEMM_VARIANT_NO_WIDE = 5,     // auto without the 128 x 256 tile
+	GEMM_VARIANT_DEEP_K_BIG = 6,  // GemmExtra::prefer_big_tiles for every product
+	GEMM_VARIANT_LEGACY = 10,     // from here up: the non-pipelined kernel (k_trim / tri_skip / stair_nb are refused)
+	GEMM_VARIANT_LEGACY_128 = 11, // non-pipelined 128 x 128 tile
+	GEMM_VARIANT_LEGACY_64 = 12,  // non-pipelined 64 x 64 tile
+};
+
+// The dense dispatch of gemm_dev as data (gemm.hip: gemm_orient, gemm_plan): pure host integer logic, no device needed
+// (faer_hip_debug_gemm_plan).  GemmProblem is a product past the level-2 exits, in elements and element strides.
+struct GemmProblem {
+	idx_t m, n, k;
+	int elem_bytes;
+	DstKind kind;
+	bool add;
+	int alpha_sign; // 1: alpha == 1, -1: alpha == -1, 0: any other value
+	idx_t drs, dcs, ars, acs, brs, bcs;
+	bool indexed, diag; // GemmExtra::row_idx or col_idx / diag given
+	int a_struct, b_struct, k_trim;
+	idx_t tri_skip, stair_nb, stair_gap, stair_row0;
+	bool prefer_big_tiles;
+	int variant;
+	bool transposed; // set by gemm_orient
+};
+enum GemmTile {
+	GEMM_TILE_EXTRA64 = 0, // gemm_kernel<EXTRA>: structured operands, diag scaling
+	GEMM_TILE_PIPE64 = 1,  // gemm_kernel_p
+	GEMM_TILE_PIPE128 = 2,
+	GEMM_TILE_PIPE_WIDE = 3, // 128 x 256, eight wavefronts
+	GEMM_TILE_LEGACY64 = 4,	 // gemm_kernel: pointer-addressed loaders, any strides
+	GEMM_TILE_LEGACY128 = 5,
+};
+struct GemmPlan {
+	bool transposed;
+	bool tri_skip_split; // tri_skip on operands the pipelined loaders cannot address: two plain products (only akm, bkm, routes set besides)
+	GemmTile tile;
+	bool akm, bkm;	  // K-major loaders
+	int bm, bn, ntm, ntn;
+	int tri_enum, tri_off;
+	int splits, k_per_split;
+	int fast_io;
+	int prof_class;
+	unsigned routes; // bit r: FaerHipRoute r counts once for this launch
+};
+bool gemm_orient(GemmProblem &p);				  // puts the problem into the orientation the kernels run; true if it transposed
+const char *gemm_plan(const GemmProblem &p, GemmPlan &plan); // nullptr, or why the product is refused (gemm_dev aborts with it)
 
 // route counters of the GEMM / TRSM dispatch (faer_hip_debug_route_counts): thread-local, defined in gemm.hip
 extern thread_local long long g_route_counts[FaerHipRoute_Count];

@@ -1107,23 +1107,17 @@ template <typename T> void fill_dev(MatV<T> A, DstKind kind, T value) { fill_ext
 // ------------------------------------------------------------------------------------------------
 // host dispatch
 // ------------------------------------------------------------------------------------------------
-template <typename T, int BM, int BN, int WM, int WN, bool EXTRA>
-static void launch_cfg(const GemmArgs<T> &g, bool akm, bool bkm, int splits)
+// loader shapes of one tile: f(AKM, BKM) with the pair as compile-time constants
+template <typename F> static void with_loaders(bool akm, bool bkm, F f)
 {
-	constexpr int BK = 16;
-	constexpr int NT = WM * WN * 64;
-	int nblocks = g.tri_enum ? g.ntm * (g.ntm + 1) / 2 : g.ntm * g.ntn;
-	dim3 grid((unsigned) nblocks, 1, (unsigned) splits), block(NT);
-	hipStream_t s = ctx().stream;
 	if (akm && bkm)
-		hipLaunchKernelGGL((gemm_kernel<T, BM, BN, BK, WM, WN, true, true, EXTRA>), grid, block, 0, s, g);
+		f(std::true_type(), std::true_type());
 	else if (akm && !bkm)
-		hipLaunchKernelGGL((gemm_kernel<T, BM, BN, BK, WM, WN, true, false, EXTRA>), grid, block, 0, s, g);
+		f(std::true_type(), std::false_type());
 	else if (!akm && bkm)
-		hipLaunchKernelGGL((gemm_kernel<T, BM, BN, BK, WM, WN, false, true, EXTRA>), grid, block, 0, s, g);
+		f(std::false_type(), std::true_type());
 	else
-		hipLaunchKernelGGL((gemm_kernel<T, BM, BN, BK, WM, WN, false, false, EXTRA>), grid, block, 0, s, g);
-	FH_HIP(hipGetLastError());
+		f(std::false_type(), std::false_type());
 }
 
 // tiles of the lower triangle in the first `rows` tile rows: square tiles, or BM x 2 BM tiles (tile row tm holds tm / 2 + 1)
@@ -1135,48 +1129,212 @@ static inline int tri_tiles(int rows, bool wide)
 	return (rows & 1) ? (p + 1) * (p + 1) : p * (p + 1);
 }
 
-// software-pipelined dense kernel (gemm_kernel_p)
-template <typename T, int BM, int BN, int WM, int WN> static void launch_cfg_p(const GemmArgs<T> &g, bool akm, bool bkm, int splits)
+// one launch of the software-pipelined dense kernel (gemm_kernel_p) or of the pointer-addressed one (gemm_kernel)
+template <typename T, int BM, int BN, int WM, int WN, bool PIPELINED, bool EXTRA = false>
+static void launch_tile(const GemmArgs<T> &g, const GemmPlan &plan)
 {
 	constexpr int BK = 16;
-	constexpr int PF = (BM * BN >= 128 * 128) ? 1 : 4; // register prefetch depth (tiles)
+	constexpr int PF = (BM * BN >= 128 * 128) ? 1 : 4; // register prefetch depth (tiles) of the pipelined kernel
 	constexpr int NT = WM * WN * 64;
 	const int nblocks = g.tri_enum ? tri_tiles(g.ntm, BN == 2 * BM) - g.tri_off : g.ntm * g.ntn;
-	dim3 grid((unsigned) nblocks, 1, (unsigned) splits), block(NT);
+	dim3 grid((unsigned) nblocks, 1, (unsigned) plan.splits), block(NT);
 	hipStream_t s = ctx().stream;
-	const unsigned dyn = 0u;
-	if (akm && bkm)
-		hipLaunchKernelGGL((gemm_kernel_p<T, BM, BN, BK, WM, WN, true, true, PF>), grid, block, dyn, s, g);
-	else if (akm && !bkm)
-		hipLaunchKernelGGL((gemm_kernel_p<T, BM, BN, BK, WM, WN, true, false, PF>), grid, block, dyn, s, g);
-	else if (!akm && bkm)
-		hipLaunchKernelGGL((gemm_kernel_p<T, BM, BN, BK, WM, WN, false, true, PF>), grid, block, dyn, s, g);
-	else
-		hipLaunchKernelGGL((gemm_kernel_p<T, BM, BN, BK, WM, WN, false, false, PF>), grid, block, dyn, s, g);
+	with_loaders(plan.akm, plan.bkm, [&](auto akm, auto bkm) {
+		if constexpr (PIPELINED)
+			hipLaunchKernelGGL((gemm_kernel_p<T, BM, BN, BK, WM, WN, decltype(akm)::value, decltype(bkm)::value, PF>), grid, block, 0, s, g);
+		else
+			hipLaunchKernelGGL((gemm_kernel<T, BM, BN, BK, WM, WN, decltype(akm)::value, decltype(bkm)::value, EXTRA>), grid, block, 0, s, g);
+	});
 	FH_HIP(hipGetLastError());
 }
 
 thread_local long long g_route_counts[FaerHipRoute_Count];
 
+// Upper(dst) == Lower(dst^T); dst^T = B^T diag A^T (diag sits between lhs and rhs in both orientations; the loader applies
+// it to the rhs rows).  A row-major Full dst is transposed too: the kernels prefer the unit dst stride along m.
+bool gemm_orient(GemmProblem &p)
+{
+	p.transposed = (p.kind == DST_UPPER) || (p.kind == DST_FULL && iabs(p.dcs) == 1 && iabs(p.drs) != 1 && !p.indexed);
+	if (!p.transposed)
+		return false;
+	std::swap(p.m, p.n);
+	std::swap(p.drs, p.dcs);
+	std::swap(p.ars, p.bcs);
+	std::swap(p.acs, p.brs);
+	if (p.k_trim)
+		p.k_trim = 3 - p.k_trim;
+	static const int tr[7] = {0, 2, 1, 4, 3, 6, 5}; // FaerBlock of the transposed operand
+	const int as = tr[p.b_struct], bs = tr[p.a_struct];
+	p.a_struct = as;
+	p.b_struct = bs;
+	if (p.kind == DST_UPPER)
+		p.kind = DST_LOWER;
+	return true;
+}
+
+// block tile and route counter of each GemmTile
+static const struct {
+	int bm, bn;
+	FaerHipRoute route;
+} g_gemm_tiles[] = {
+	{64, 64, FaerHipRoute_GemmExtra64},    {64, 64, FaerHipRoute_GemmPipe64},   {128, 128, FaerHipRoute_GemmPipe128},
+	{128, 256, FaerHipRoute_GemmPipeWide}, {64, 64, FaerHipRoute_GemmLegacy64}, {128, 128, FaerHipRoute_GemmLegacy128},
+};
+
+// Every decision of the dense dispatch for an oriented problem, in the order of precedence:
+//   1. the operands pick the kernel family: structured operands or diag scaling -> the 64 x 64 EXTRA kernel; a forced legacy
+//      variant, or strides the 32-bit buffer offsets of the pipelined loaders cannot express -> the pointer-addressed kernel
+//      (with tri_skip: two plain products instead); everything else -> the pipelined kernel;
+//   2. the tile count picks big (128 x 128) or small (64 x 64) tiles, the variant or prefer_big_tiles may overrule it;
+//   3. big plain products may take the 128 x 256 tile (deep K and many tiles, or forced);
+//   4. tile enumeration, split-K and the fused epilogue follow from the tile.
+const char *gemm_plan(const GemmProblem &p, GemmPlan &plan)
+{
+	plan = GemmPlan{};
+	plan.transposed = p.transposed;
+	plan.routes = p.transposed ? 1u << FaerHipRoute_GemmTransposed : 0u;
+	const idx_t m = p.m, n = p.n, k = p.k;
+	const int variant = p.variant;
+	const bool lower = p.kind == DST_LOWER;
+	const bool extra_path = p.diag || p.a_struct || p.b_struct;
+	if ((p.k_trim || p.tri_skip || p.stair_nb) && (extra_path || p.indexed || variant >= GEMM_VARIANT_LEGACY))
+		return "gemm: k_trim / tri_skip / stair_nb need the plain dense kernel";
+	if (p.stair_nb && !(lower && !p.transposed && p.stair_nb > 0 && p.stair_gap >= 0 && p.stair_row0 >= 0))
+		return "gemm: stair_nb needs a lower, untransposed dst";
+
+	// loader shapes: K-major when the k stride is the unit one (and the mn stride is not)
+	const bool akm = plan.akm = iabs(p.acs) == 1 && iabs(p.ars) != 1;
+	const bool bkm = plan.bkm = iabs(p.brs) == 1 && iabs(p.bcs) != 1;
+
+	// Big or small tiles.  Measured on MI355X (profiles/r01_call2_gemm_variants.txt): the pipelined 128 x 128 tile is ahead of
+	// the 64 x 64 tile from N = 2048 (256 big tiles) upwards and 12 % ahead at N = 8192; below that the small tile gives the
+	// 256 CUs more workgroups.
+	const idx_t tiles128 = ((m + 127) / 128) * ((n + 127) / 128) / (lower ? 2 : 1);
+	bool big = tiles128 >= 256;
+	if (variant == GEMM_VARIANT_FORCE_128 || variant == GEMM_VARIANT_LEGACY_128 || variant == GEMM_VARIANT_FORCE_WIDE)
+		big = true;
+	if (variant == GEMM_VARIANT_FORCE_64 || variant == GEMM_VARIANT_LEGACY_64)
+		big = false;
+	// (A/B, tools/gpu_qr_square_gemm_ab.py): short-wide / tall-narrow FULL outputs with a deep K -- the V^H A products of the QR
+	// block applications, 128 x n with K = rows -- on 128 x 128 tiles with more K slices instead of 64 x 64 tiles
+	if ((variant == GEMM_VARIANT_DEEP_K_BIG || (variant == GEMM_VARIANT_AUTO && p.prefer_big_tiles)) && !big && !lower && k >= 2048 &&
+	    ((m >= 128 && n >= 1024) || (n >= 128 && m >= 1024)))
+		big = true;
+
+	bool legacy = variant >= GEMM_VARIANT_LEGACY;
+	{
+		// the pipelined kernel addresses full operand tiles through 32-bit buffer offsets (see its loaders): operands with
+		// negative strides, or whose per-lane / per-element offsets inside a tile row do not fit, go to the non-pipelined kernel
+		const idx_t ts = p.elem_bytes;
+		const bool a_ok = p.ars >= 0 && p.acs >= 0 && (akm || ((m - 1) * p.ars + 32 * p.acs) * ts < (1L << 31));
+		// (K-major B: lane offset <= 15 brs + 31 bcs, element offsets <= (BN - 16) bcs with BN <= 256; its descriptor ends where
+		// column N begins, which is only the end of the last column's 16-row tile if the columns are >= 16 elements apart:
+		// broadcast views (cs == 0) and overlapping columns (0 < cs < 16) keep the pointer loaders -- ADVICE r04)
+		const bool b_ok = p.brs >= 0 && p.bcs >= 0 &&
+				  (bkm ? (p.bcs >= 16 && (16 * p.brs + 256 * p.bcs) * ts < (1L << 31)) : ((n - 1) * p.bcs + 32 * p.brs) * ts < (1L << 31));
+		if (!(a_ok && b_ok) && !legacy) {
+			if (p.tri_skip && !p.k_trim && !p.stair_nb) {
+				// (the Cholesky look-ahead's merged update on a view the buffer-addressed loaders cannot take -- negative
+				// strides, a huge leading dimension: ADVICE r04.)  The pointer-addressed kernel has no tile skip: the
+				// rectangle below the skipped rows, then the lower triangle right of it, as two plain products.
+				if (!(lower && m == n && p.tri_skip < m))
+					return "gemm: tri_skip needs a square lower dst";
+				plan.tri_skip_split = true;
+				plan.routes |= 1u << FaerHipRoute_GemmTriSkipSplit;
+				return nullptr;
+			}
+			if (p.k_trim || p.tri_skip || p.stair_nb)
+				return "gemm: operand strides out of range for this product";
+			legacy = true;
+		}
+	}
+
+	// Eight wavefronts of 64 x 64 per workgroup (128 x 256 block tile, one workgroup per CU) for large plain FULL products
+	// with a deep K: the A tile is shared by four wavefront columns, the B tile by two rows -- 25 % fewer global loads and
+	// LDS stores per flop than four wavefronts on 128 x 128, same LDS reads per MFMA.  DGEMM N = 8192: 68.6 -> 71.3 TFLOP/s
+	// in one visit (256 x 128: 70.9; raster group sizes 2 .. 32 make no difference; four wavefronts of 128 x 64 on the same
+	// block tile spill in the main loop: 12 TFLOP/s).  One workgroup per CU means nobody covers a workgroup's accumulate
+	// epilogue, so the short-K updates of the factorizations stay on the 128 x 128 tile (tools/gpu_gemm_wide_ab.py:
+	// r = 8192: K = 512 -2 %, K = 2048 +1.4 %, K = 8192 +2.9 %; r = 15360: +-0.3 %), and so does every lower dst (its
+	// 128 x 256 tiles on the diagonal waste more: -5 .. -11 %; the trapezoid enumeration is kept reachable for tests).
+	const bool plain = !extra_path && !p.indexed;
+	const bool wide_ok = plain && (lower ? m == n : !p.k_trim);
+	const idx_t tiles_wide = ((m + 127) / 128) * ((n + 255) / 256);
+	const bool wide_auto = !lower && k >= 2048 && tiles_wide >= 512;
+	const bool wide = wide_ok && big && !legacy && (variant == GEMM_VARIANT_FORCE_WIDE || (variant == GEMM_VARIANT_AUTO && wide_auto));
+
+	plan.tile = extra_path ? GEMM_TILE_EXTRA64
+		    : wide ? GEMM_TILE_PIPE_WIDE
+		    : legacy ? (big ? GEMM_TILE_LEGACY128 : GEMM_TILE_LEGACY64)
+			     : (big ? GEMM_TILE_PIPE128 : GEMM_TILE_PIPE64);
+	const int bm = plan.bm = g_gemm_tiles[plan.tile].bm, bn = plan.bn = g_gemm_tiles[plan.tile].bn;
+	plan.ntm = (int) ((m + bm - 1) / bm);
+	plan.ntn = (int) ((n + bn - 1) / bn);
+	plan.tri_enum = (lower && m == n && !p.stair_nb) ? 1 : 0;
+	if (p.tri_skip) {
+		if (!(plan.tri_enum && p.tri_skip % bm == 0 && p.tri_skip < m))
+			return "gemm: tri_skip needs a square lower dst and a tile-aligned skip";
+		plan.tri_off = tri_tiles((int) (p.tri_skip / bm), bn == 2 * bm);
+	}
+
+	// Deep-K products with few output tiles are split along K.  Rectangular outputs (the V^H A / V^H V products of QR:
+	// K = rows of the panel, a few tiles of output) split from K = 1024 in slices of >= 256 (measured: square QR
+	// N = 4096 99.6 -> 80.2 ms); triangular outputs (the diagonal-block updates of the blocked Cholesky, which sit
+	// on its critical chain) keep the coarser rule, the finer one cost the N = 16384 factorization 0.6 ms.
+	const idx_t tiles = plan.tri_enum ? (idx_t) tri_tiles(plan.ntm, bn == 2 * bm) - plan.tri_off : (idx_t) plan.ntm * plan.ntn;
+	const idx_t mink = lower ? 4096 : 1024, chunk = lower ? 1024 : 256;
+	int splits = 1;
+	if (tiles < 256 && k >= mink && !p.indexed && !p.k_trim && !p.stair_nb) {
+		splits = (int) ((512 + tiles - 1) / tiles);
+		idx_t max_splits = k / chunk;
+		if (splits > max_splits)
+			splits = (int) max_splits;
+		if (splits > 1024)
+			splits = 1024;
+		if (splits < 1)
+			splits = 1;
+	}
+	idx_t kps = (k + splits - 1) / splits;
+	kps = (kps + 15) / 16 * 16;
+	plan.splits = splits = (int) ((k + kps - 1) / kps);
+	plan.k_per_split = (int) kps;
+
+	// fused epilogue of the pipelined kernel: interior tiles of a plain column-major dst
+	// (the wave-uniform byte offsets of a tile, < 64 dcs sizeof(T), and the per-lane ones, < 16 dcs sizeof(T), are 32-bit)
+	if (plain && !legacy && splits == 1 && p.drs == 1 && p.dcs > 0 && p.dcs < (1L << 21) && !p.stair_nb)
+		plan.fast_io = !p.add ? 1 : p.alpha_sign == 1 ? 2 : p.alpha_sign == -1 ? 3 : 0;
+	// (profile class 0: the big pipelined tiles -- the trailing updates of the factorizations, the headline product)
+	plan.prof_class = plan.tile == GEMM_TILE_PIPE128 || plan.tile == GEMM_TILE_PIPE_WIDE ? 0 : -1;
+
+	if (plan.tri_enum)
+		plan.routes |= 1u << FaerHipRoute_GemmTriEnum;
+	if (splits > 1)
+		plan.routes |= 1u << FaerHipRoute_GemmSplitK;
+	if (plan.fast_io)
+		plan.routes |= 1u << (FaerHipRoute_GemmFastIo1 + plan.fast_io - 1);
+	plan.routes |= 1u << g_gemm_tiles[plan.tile].route;
+	return nullptr;
+}
+
 template <typename T>
 void gemm_dev(MatV<T> C, DstKind kind, bool add, MatV<const T> A, MatV<const T> B, T alpha, const GemmExtra<T> *extra)
 {
 	FH_CHECK(A.nrows == C.nrows && B.ncols == C.ncols && A.ncols == B.nrows, "gemm: shape mismatch");
-	idx_t m = C.nrows, n = C.ncols, k = A.ncols;
-	if (m == 0 || n == 0)
+	if (C.nrows == 0 || C.ncols == 0)
 		return;
-	if (k == 0) { // faer/src/linalg/matmul/mod.rs:1190-1198
+	if (A.ncols == 0) { // faer/src/linalg/matmul/mod.rs:1190-1198
 		route_hit(FaerHipRoute_GemmZeroK);
 		if (!add)
 			fill_ext<T>(C, kind, (T) 0, extra);
 		return;
 	}
-	FH_CHECK(m < (1L << 31) && n < (1L << 31) && k < (1L << 31), "gemm: dimension too large");
+	FH_CHECK(C.nrows < (1L << 31) && C.ncols < (1L << 31) && A.ncols < (1L << 31), "gemm: dimension too large");
 	GemmExtra<T> ex;
 	if (extra)
 		ex = *extra;
 	// level-2 shapes leave for the streaming kernels (matmul/mod.rs:1215-1310: matvec / rank_update dispatch)
-	if (kind == DST_FULL && !ex.row_idx && !ex.col_idx && !ex.diag && !ex.a_struct && !ex.b_struct && !ex.inplace) {
+	if (kind == DST_FULL && !ex.row_idx && !ex.col_idx && !ex.diag && !ex.a_struct && !ex.b_struct) {
+		const idx_t m = C.nrows, n = C.ncols, k = A.ncols;
 		if (k == 1 && m * n >= 1) {
 			route_hit(FaerHipRoute_GemmRank1);
 			rank1_dev<T>(C, add, A.p, A.rs, B.p, B.cs, alpha);
@@ -1192,35 +1350,34 @@ void gemm_dev(MatV<T> C, DstKind kind, bool add, MatV<const T> A, MatV<const T> 
 			return;
 		}
 	}
-	const bool indexed = ex.row_idx || ex.col_idx;
-	// Upper(dst) == Lower(dst^T); dst^T = B^T diag A^T.  Also prefer the unit dst stride along m.
-	bool transpose = (kind == DST_UPPER) || (kind == DST_FULL && iabs(C.cs) == 1 && iabs(C.rs) != 1 && !indexed);
-	if (transpose) {
-		route_hit(FaerHipRoute_GemmTransposed);
-		MatV<T> Ct = C.t();
-		MatV<const T> At = B.t(), Bt = A.t();
-		C = Ct;
+
+	GemmProblem p{C.nrows, C.ncols, A.ncols, (int) sizeof(T), kind, add, alpha == (T) 1 ? 1 : alpha == (T) -1 ? -1 : 0,
+		      C.rs, C.cs, A.rs, A.cs, B.rs, B.cs, ex.row_idx || ex.col_idx, ex.diag != nullptr, ex.a_struct, ex.b_struct, ex.k_trim,
+		      ex.tri_skip, ex.stair_nb, ex.stair_gap, ex.stair_row0, ex.prefer_big_tiles, ctx().gemm_variant, false};
+	if (gemm_orient(p)) {
+		const MatV<const T> At = B.t(), Bt = A.t();
+		C = C.t();
 		A = At;
 		B = Bt;
 		std::swap(ex.row_idx, ex.col_idx);
-		if (ex.inplace)
-			ex.inplace = 3 - ex.inplace; // the aliased operand changes sides with the transposition
-		if (ex.k_trim)
-			ex.k_trim = 3 - ex.k_trim;
-		std::swap(m, n);
-		static const int tr[7] = {0, 2, 1, 4, 3, 6, 5}; // FaerBlock of the transposed operand
-		const int as = tr[ex.b_struct], bs = tr[ex.a_struct];
-		ex.a_struct = as;
-		ex.b_struct = bs;
-		if (kind == DST_UPPER)
-			kind = DST_LOWER;
-		// diag sits between lhs and rhs in both orientations; the loader applies it to the rhs rows (k)
+	}
+	GemmPlan plan;
+	const char *refusal = gemm_plan(p, plan);
+	FH_CHECK(!refusal, refusal);
+	for (int r = 0; r < (int) FaerHipRoute_Count; ++r)
+		if ((plan.routes >> r) & 1)
+			route_hit((FaerHipRoute) r);
+	if (plan.tri_skip_split) {
+		const idx_t sk = p.tri_skip, m = p.m, k = p.k;
+		gemm_dev<T>(C.sub(sk, 0, m - sk, sk), DST_FULL, add, A.sub(sk, 0, m - sk, k), B.sub(0, 0, k, sk), alpha, nullptr);
+		gemm_dev<T>(C.sub(sk, sk, m - sk, m - sk), DST_LOWER, add, A.sub(sk, 0, m - sk, k), B.sub(0, sk, k, m - sk), alpha, nullptr);
+		return;
 	}
 
 	GemmArgs<T> g;
-	g.M = (int) m;
-	g.N = (int) n;
-	g.K = (int) k;
+	g.M = (int) p.m;
+	g.N = (int) p.n;
+	g.K = (int) p.k;
 	g.dst = C.p;
 	g.drs = C.rs;
 	g.dcs = C.cs;
@@ -1232,226 +1389,64 @@ void gemm_dev(MatV<T> C, DstKind kind, bool add, MatV<const T> A, MatV<const T> 
 	g.bcs = B.cs;
 	g.alpha = alpha;
 	g.add = add ? 1 : 0;
-	g.lower = kind == DST_LOWER ? 1 : 0;
-	g.atomic = 0;
-	g.ws = nullptr;
+	g.lower = p.kind == DST_LOWER ? 1 : 0;
 	g.row_idx = ex.row_idx;
 	g.col_idx = ex.col_idx;
 	g.idx64 = ex.idx64;
 	g.diag = ex.diag;
 	g.diag_stride = ex.diag_stride;
-	g.a_struct = ex.a_struct;
-	g.b_struct = ex.b_struct;
+	g.a_struct = p.a_struct;
+	g.b_struct = p.b_struct;
 	g.dst_strict = ex.dst_strict ? 1 : 0;
-	g.k_trim = ex.k_trim;
-	g.tri_off = 0;
-	g.stair_nb = (int) ex.stair_nb;
-	g.stair_gap = (int) ex.stair_gap;
-	g.stair_row0 = (int) ex.stair_row0;
-	{
-		g.raster_g = 8; // (2 ... 32 measured within 0.3 % of each other at N = 8192: profiles/notes/DESIGN_history_r01_r05.md 3.1)
-	}
-	const bool extra_path = ex.diag || ex.a_struct || ex.b_struct;
-	if (ex.k_trim || ex.tri_skip || ex.stair_nb)
-		FH_CHECK(!extra_path && !indexed && !ex.inplace && ctx().gemm_variant < 10, "gemm: k_trim / tri_skip / stair_nb need the plain dense kernel");
-	if (ex.stair_nb)
-		FH_CHECK(g.lower && !transpose && ex.stair_nb > 0 && ex.stair_gap >= 0 && ex.stair_row0 >= 0, "gemm: stair_nb needs a lower, untransposed dst");
-
-	// loader shapes: K-major when the k stride is the unit one (and the mn stride is not)
-	const bool akm = iabs(A.cs) == 1 && iabs(A.rs) != 1;
-	const bool bkm = iabs(B.rs) == 1 && iabs(B.cs) != 1;
-
-	// tile config.  ctx().gemm_variant: 0 = auto (pipelined kernels); 1 / 2 = force 128 / 64 tiles (pipelined);
-	// 11 / 12 = force 128 / 64 tiles on the non-pipelined kernel (A/B measurements).
-	// Measured on MI355X (profiles/r01_call2_gemm_variants.txt): the pipelined 128 x 128 tile is ahead of the
-	// 64 x 64 tile from N = 2048 (256 big tiles) upwards and 12 % ahead at N = 8192; below that the small tile
-	// gives the 256 CUs more workgroups.
-	const int variant = ctx().gemm_variant;
-	const idx_t tiles128 = ((m + 127) / 128) * ((n + 127) / 128) / (kind == DST_LOWER ? 2 : 1);
-	bool big = tiles128 >= 256;
-	if (variant == 1 || variant == 11 || variant == 3)
-		big = true;
-	if (variant == 2 || variant == 12)
-		big = false;
-	// variant 6 (A/B, tools/gpu_qr_square_gemm_ab.py): short-wide / tall-narrow FULL outputs with a deep K -- the V^H A products of the QR
-	// block applications, 128 x n with K = rows -- on 128 x 128 tiles with more K slices instead of 64 x 64 tiles
-	if ((variant == 6 || (variant == 0 && ex.prefer_big_tiles)) && !big && kind == DST_FULL && k >= 2048 && ((m >= 128 && n >= 1024) || (n >= 128 && m >= 1024)))
-		big = true;
-	// Eight wavefronts of 64 x 64 per workgroup (128 x 256 block tile, one workgroup per CU) for large plain FULL products
-	// with a deep K: the A tile is shared by four wavefront columns, the B tile by two rows -- 25 % fewer global loads and
-	// LDS stores per flop than four wavefronts on 128 x 128, same LDS reads per MFMA.  DGEMM N = 8192: 68.6 -> 71.3 TFLOP/s
-	// in one visit (256 x 128: 70.9; raster group sizes 2 .. 32 make no difference; four wavefronts of 128 x 64 on the same
-	// block tile spill in the main loop: 12 TFLOP/s).  One workgroup per CU means nobody covers a workgroup's accumulate
-	// epilogue, so the short-K updates of the factorizations stay on the 128 x 128 tile (tools/gpu_gemm_wide_ab.py:
-	// r = 8192: K = 512 -2 %, K = 2048 +1.4 %, K = 8192 +2.9 %; r = 15360: +-0.3 %), and so does every lower dst (its
-	// 128 x 256 tiles on the diagonal waste more: -5 .. -11 %; the trapezoid enumeration is kept reachable for tests).
-	// variant 3 forces the wide tile (full and square lower), 5 forbids it.
-	bool legacy = variant >= 10;
-	{
-		// the pipelined kernel addresses full operand tiles through 32-bit buffer offsets (see its loaders): operands with
-		// negative strides, or whose per-lane / per-element offsets inside a tile row do not fit, go to the non-pipelined kernel
-		const idx_t ts = (idx_t) sizeof(T);
-		const bool a_ok = A.rs >= 0 && A.cs >= 0 && (akm || ((m - 1) * A.rs + 32 * A.cs) * ts < (1L << 31));
-		// (K-major B: lane offset <= 15 brs + 31 bcs, element offsets <= (BN - 16) bcs with BN <= 256; its descriptor ends where
-		// column N begins, which is only the end of the last column's 16-row tile if the columns are >= 16 elements apart:
-		// broadcast views (cs == 0) and overlapping columns (0 < cs < 16) keep the pointer loaders -- ADVICE r04)
-		const bool b_ok = B.rs >= 0 && B.cs >= 0 &&
-				  (bkm ? (B.cs >= 16 && (16 * B.rs + 256 * B.cs) * ts < (1L << 31)) : ((n - 1) * B.cs + 32 * B.rs) * ts < (1L << 31));
-		if (!(a_ok && b_ok) && !legacy) {
-			if (ex.tri_skip && !ex.k_trim && !ex.stair_nb && !ex.inplace) {
-				// (the Cholesky look-ahead's merged update on a view the buffer-addressed loaders cannot take -- negative
-				// strides, a huge leading dimension: ADVICE r04.)  The pointer-addressed kernel has no tile skip: the
-				// rectangle below the skipped rows, then the lower triangle right of it, as two plain products.
-				const idx_t sk = ex.tri_skip;
-				FH_CHECK(kind == DST_LOWER && m == n && sk < m, "gemm: tri_skip needs a square lower dst");
-				route_hit(FaerHipRoute_GemmTriSkipSplit);
-				gemm_dev<T>(C.sub(sk, 0, m - sk, sk), DST_FULL, add, A.sub(sk, 0, m - sk, k), B.sub(0, 0, k, sk), alpha, nullptr);
-				gemm_dev<T>(C.sub(sk, sk, m - sk, m - sk), DST_LOWER, add, A.sub(sk, 0, m - sk, k), B.sub(0, sk, k, m - sk), alpha, nullptr);
-				return;
-			}
-			FH_CHECK(!ex.k_trim && !ex.tri_skip && !ex.stair_nb && !ex.inplace, "gemm: operand strides out of range for this product");
-			legacy = true;
-		}
-	}
-	const bool plain = !ex.inplace && !ex.diag && !ex.a_struct && !ex.b_struct && !ex.row_idx && !ex.col_idx;
-	const bool wide_ok = plain && (kind == DST_FULL ? !ex.k_trim : (m == n));
-	const idx_t tiles_wide = ((m + 127) / 128) * ((n + 255) / 256);
-	const bool wide_auto = kind == DST_FULL && k >= 2048 && tiles_wide >= 512;
-	const int wide = wide_ok && big && variant != 5 && !legacy && (variant == 3 || (variant == 0 && wide_auto)) ? 1 : 0;
-	// in-place product (ex.inplace): the aliased operand and dst share rows (transposed orientation: A and C
-	// share their rows, one tile must cover all of N) or columns (B and C share their columns, one tile must
-	// cover all of M).  A 32-wide tile along the free dimension keeps the launch wide for skinny panels.
-	int bm = big ? 128 : 64, bn = bm;
-	int shape = big ? 0 : 1; // 0: 128x128  1: 64x64  2: 32x128  3: 128x32
-	if (ex.inplace) {
-		FH_CHECK(!extra_path && kind == DST_FULL && !indexed, "gemm: in-place product must be a plain one");
-		// long free dimension: the 128 x 128 tile (fewer, fatter workgroups; one per CU is enough to fill the
-		// chip); short one: 32-wide tiles keep the launch wide.  Either way ONE tile spans the aliased dimension.
-		if (ex.inplace == 2) { // A aliases C: all of N inside one tile
-			FH_CHECK(n <= 128 && k == n, "gemm: in-place (A) product needs N == K <= 128");
-			if (m >= 4096) {
-				bm = bn = 128;
-				shape = 0;
-			} else {
-				bm = 32;
-				bn = 128;
-				shape = 2;
-			}
-		} else { // B aliases C: all of M inside one tile
-			FH_CHECK(m <= 128 && k == m, "gemm: in-place (B) product needs M == K <= 128");
-			if (n >= 4096) {
-				bm = bn = 128;
-				shape = 0;
-			} else {
-				bm = 128;
-				bn = 32;
-				shape = 3;
-			}
-		}
-	}
-	if (extra_path) {
-		bm = bn = 64;
-		shape = 1;
-	}
-	if (wide) {
-		bm = 128;
-		bn = 256;
-		shape = 5;
-	}
-	g.ntm = (int) ((m + bm - 1) / bm);
-	g.ntn = (int) ((n + bn - 1) / bn);
-	g.tri_enum = (g.lower && m == n && !ex.stair_nb) ? 1 : 0;
-	if (ex.tri_skip) {
-		FH_CHECK(g.tri_enum && ex.tri_skip % bm == 0 && ex.tri_skip < m, "gemm: tri_skip needs a square lower dst and a tile-aligned skip");
-		const int st = (int) (ex.tri_skip / bm);
-		g.tri_off = tri_tiles(st, bn == 2 * bm);
-	}
-
-	// split-K for few-tile / deep-K products
-	idx_t tiles = g.tri_enum ? (idx_t) tri_tiles(g.ntm, bn == 2 * bm) - g.tri_off : (idx_t) g.ntm * g.ntn;
-	int splits = 1;
-	// Deep-K products with few output tiles are split along K.  Rectangular outputs (the V^H A / V^H V products of QR:
-	// K = rows of the panel, a few tiles of output) split from K = 1024 in slices of >= 256 (measured: square QR
-	// N = 4096 99.6 -> 80.2 ms); triangular outputs (the diagonal-block updates of the blocked Cholesky, which sit
-	// on its critical chain) keep the coarser rule, the finer one cost the N = 16384 factorization 0.6 ms.
-	const idx_t splitk_mink = 1024, splitk_chunk = 256;
-	const idx_t mink = kind == DST_FULL ? splitk_mink : 4096, chunk = kind == DST_FULL ? splitk_chunk : 1024;
-	if (tiles < 256 && k >= mink && !indexed && !ex.k_trim && !ex.stair_nb) {
-		splits = (int) ((512 + tiles - 1) / tiles);
-		idx_t max_splits = k / chunk;
-		if (splits > max_splits)
-			splits = (int) max_splits;
-		if (splits > 1024)
-			splits = 1024;
-		if (splits < 1)
-			splits = 1;
-	}
-	idx_t kps = (k + splits - 1) / splits;
-	kps = (kps + 15) / 16 * 16;
-	splits = (int) ((k + kps - 1) / kps);
-	g.k_per_split = (int) kps;
+	g.k_trim = p.k_trim;
+	g.stair_nb = (int) p.stair_nb;
+	g.stair_gap = (int) p.stair_gap;
+	g.stair_row0 = (int) p.stair_row0;
+	g.raster_g = 8; // (2 ... 32 measured within 0.3 % of each other at N = 8192: profiles/notes/DESIGN_history_r01_r05.md 3.1)
+	g.ntm = plan.ntm;
+	g.ntn = plan.ntn;
+	g.tri_enum = plan.tri_enum;
+	g.tri_off = plan.tri_off;
+	g.k_per_split = plan.k_per_split;
+	g.fast_io = plan.fast_io;
 	// deep-K products are split over workgroups; the slices meet in a workspace and are added in a fixed order by
 	// a second small kernel, so the result does not depend on scheduling (hardware atomics would be faster by one
 	// launch but make every QR run differ in the last bits)
-	Scratch wsb(splits > 1 ? (size_t) splits * (size_t) m * (size_t) n * sizeof(T) : 256);
+	Scratch wsb(plan.splits > 1 ? (size_t) plan.splits * (size_t) p.m * (size_t) p.n * sizeof(T) : 256);
 	g.ws = wsb.as<T>();
-	if (splits > 1)
-		g.atomic = 2;
+	g.atomic = plan.splits > 1 ? 2 : 0;
 
-	if (ex.inplace)
-		FH_CHECK(splits == 1, "gemm: in-place product cannot be split along K");
-	g.fast_io = 0;
-	{
-		// (the wave-uniform byte offsets of a tile, < 64 dcs sizeof(T), and the per-lane ones, < 16 dcs sizeof(T), are 32-bit)
-		if (plain && !legacy && splits == 1 && C.rs == 1 && C.cs > 0 && C.cs < (1L << 21) && !ex.stair_nb) {
-			if (!add)
-				g.fast_io = 1;
-			else if (alpha == (T) 1)
-				g.fast_io = 2;
-			else if (alpha == (T) -1)
-				g.fast_io = 3;
-		}
+	const double out_elems = plan.tri_enum ? 0.5 * (double) p.m * (double) (p.m + 1) - 0.5 * (double) p.tri_skip * (double) (p.tri_skip + 1)
+					       : (double) p.m * (double) p.n;
+	ProfScope prof(plan.prof_class, 2.0 * (double) p.k * out_elems);
+	prof.sp.d[0] = (long) p.m;
+	prof.sp.d[1] = (long) p.n;
+	prof.sp.d[2] = (long) p.k;
+	prof.sp.d[3] = plan.tri_enum ? 1 + (long) p.tri_skip : 0;
+	switch (plan.tile) {
+	case GEMM_TILE_EXTRA64: // triangular operands / diag scaling
+		launch_tile<T, 64, 64, 2, 2, false, true>(g, plan);
+		break;
+	case GEMM_TILE_PIPE_WIDE:
+		launch_tile<T, 128, 256, 2, 4, true>(g, plan);
+		break;
+	case GEMM_TILE_LEGACY128:
+		launch_tile<T, 128, 128, 2, 2, false>(g, plan);
+		break;
+	case GEMM_TILE_LEGACY64:
+		launch_tile<T, 64, 64, 2, 2, false>(g, plan);
+		break;
+	case GEMM_TILE_PIPE128:
+		launch_tile<T, 128, 128, 2, 2, true>(g, plan);
+		break;
+	case GEMM_TILE_PIPE64:
+		launch_tile<T, 64, 64, 2, 2, true>(g, plan);
+		break;
 	}
-	// (profile class 0: the big pipelined tiles -- the trailing updates of the factorizations, the headline product)
-	const double out_elems = g.tri_enum ? 0.5 * (double) m * (double) (m + 1) - 0.5 * (double) ex.tri_skip * (double) (ex.tri_skip + 1) : (double) m * (double) n;
-	ProfScope prof(!extra_path && !legacy && (shape == 0 || shape == 5) ? 0 : -1, 2.0 * (double) k * out_elems);
-	prof.sp.d[0] = (long) m;
-	prof.sp.d[1] = (long) n;
-	prof.sp.d[2] = (long) k;
-	prof.sp.d[3] = g.tri_enum ? 1 + (long) ex.tri_skip : 0;
-	if (g.tri_enum)
-		route_hit(FaerHipRoute_GemmTriEnum);
-	if (splits > 1)
-		route_hit(FaerHipRoute_GemmSplitK);
-	if (g.fast_io)
-		route_hit(g.fast_io == 1 ? FaerHipRoute_GemmFastIo1 : g.fast_io == 2 ? FaerHipRoute_GemmFastIo2 : FaerHipRoute_GemmFastIo3);
-	route_hit(extra_path ? FaerHipRoute_GemmExtra64
-		  : shape == 5 ? FaerHipRoute_GemmPipeWide
-		  : shape == 2 ? FaerHipRoute_GemmInplace32x128
-		  : shape == 3 ? FaerHipRoute_GemmInplace128x32
-		  : legacy ? (shape == 0 ? FaerHipRoute_GemmLegacy128 : FaerHipRoute_GemmLegacy64)
-		  : shape == 0 ? FaerHipRoute_GemmPipe128 : FaerHipRoute_GemmPipe64);
-	if (extra_path)
-		launch_cfg<T, 64, 64, 2, 2, true>(g, akm, bkm, splits); // triangular operands / diag scaling
-	else if (shape == 5)
-		launch_cfg_p<T, 128, 256, 2, 4>(g, akm, bkm, splits);
-	else if (shape == 2)
-		launch_cfg_p<T, 32, 128, 1, 4>(g, akm, bkm, splits);
-	else if (shape == 3)
-		launch_cfg_p<T, 128, 32, 4, 1>(g, akm, bkm, splits);
-	else if (legacy && shape == 0)
-		launch_cfg<T, 128, 128, 2, 2, false>(g, akm, bkm, splits);
-	else if (legacy)
-		launch_cfg<T, 64, 64, 2, 2, false>(g, akm, bkm, splits);
-	else if (shape == 0)
-		launch_cfg_p<T, 128, 128, 2, 2>(g, akm, bkm, splits);
-	else
-		launch_cfg_p<T, 64, 64, 2, 2>(g, akm, bkm, splits);
-	if (splits > 1) {
-		const idx_t total = m * n;
-		const idx_t blocks = (total + 15) / 16;
-		hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned) blocks), dim3(256), 0, ctx().stream, C.p, C.rs, C.cs, (int) m, (int) n,
-				   wsb.as<T>(), splits, alpha, add ? 1 : 0, g.lower, g.dst_strict);
+	if (plan.splits > 1) {
+		const idx_t blocks = (p.m * p.n + 15) / 16;
+		hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned) blocks), dim3(256), 0, ctx().stream, C.p, C.rs, C.cs, g.M, g.N, wsb.as<T>(),
+				   plan.splits, alpha, g.add, g.lower, g.dst_strict);
 		FH_HIP(hipGetLastError());
 	}
 }

@@ -658,8 +658,26 @@ FAER_HIP_API void *faer_hip_malloc(size_t bytes);
 FAER_HIP_API void faer_hip_free(void *ptr);
 FAER_HIP_API void faer_hip_memcpy_h2d(void *dst_device, const void *src_host, size_t bytes);
 FAER_HIP_API void faer_hip_memcpy_d2h(void *dst_host, const void *src_device, size_t bytes);
-/* Tuning knob used by bench.py / tests: selects the GEMM tile variant (0 = auto). */
+/* Tuning knob used by bench.py / tests: the GEMM tile variant of the calling thread.  0 = auto (the rules of the dispatch),
+ * 1 / 2 = force the pipelined 128 x 128 / 64 x 64 tile, 3 = force the 128 x 256 tile wherever it can run (plain full and square
+ * lower products), 5 = auto without the 128 x 256 tile, 6 = 128 x 128 tiles for every short-wide / tall-narrow full product with
+ * K >= 2048 (what the QR block applications ask for themselves), 11 / 12 = the non-pipelined kernel on 128 x 128 / 64 x 64
+ * tiles.  Structured operands and diag scaling always run the 64 x 64 kernel made for them. */
 FAER_HIP_API void faer_hip_set_gemm_variant(int variant);
+/* Host-side dispatch of the dense GEMM, callable without a GPU (unit tests): what gemm_dev decides for a product that has not
+ * left for a level-2 kernel (K >= 1; rank-1, matrix-vector and skinny shapes are decided by those kernels themselves).
+ * problem[24] = {m, n, k, bytes per element (4 / 8), dst kind (FaerHipDstKind), add (0 / 1), alpha (1: +1, -1: -1, 0: another value),
+ * dst row stride, dst col stride, lhs row, lhs col, rhs row, rhs col stride (elements), index arrays given (0 / 1), diag given (0 / 1),
+ * lhs FaerBlock, rhs FaerBlock, k_trim, tri_skip, stair_nb, stair_gap, stair_row0, prefer_big_tiles (0 / 1), variant (see
+ * faer_hip_set_gemm_variant)}, as the caller passes the product (before any transposition).
+ * plan[16] = {transposed (the product runs on dst^T; tile counts and loaders below refer to that orientation), tile kind (0 the 64 x 64
+ * kernel for structured operands / diag, 1 / 2 / 3 pipelined 64 x 64 / 128 x 128 / 128 x 256, 4 / 5 non-pipelined 64 x 64 / 128 x 128),
+ * tri_skip split into two plain products (0 / 1; then only the loaders and the routes are set besides), lhs K-major loader, rhs K-major loader, tile rows, tile
+ * columns, tiles along m, tiles along n, triangular tile enumeration (0 / 1), first tile of it, K splits, K per split, fused epilogue
+ * (0 none, 1 Replace, 2 / 3 Add with alpha +1 / -1), profile class (0 big pipelined tile, -1 none), routes (bit r: FaerHipRoute r counts)}.
+ * Returns 0; 1 if the library refuses the product (it would abort with *refusal, a static string; `refusal` may be NULL); -1 if
+ * `problem` is not a dense product (a dimension < 1 or >= 2^31, an element size other than 4 / 8, codes out of range). */
+FAER_HIP_API int faer_hip_debug_gemm_plan(const long long problem[24], int plan[16], const char **refusal);
 /* Debugging aid.  `which`: 0 = the caller's stream, 1 / 2 = the internal bulk / panel look-ahead stream; writes
  * {XCC id, HW_ID} of the CU each of `nblocks` probe workgroups ran on (2 * nblocks words of host memory). */
 FAER_HIP_API void faer_hip_debug_stream_xcc(int which, int nblocks, unsigned *out_host);
@@ -697,7 +715,8 @@ FAER_HIP_API long faer_hip_debug_qr_one_pass_columns(void);
 /* tests: which GEMM / TRSM routes the calling thread's library calls took.  One counter per route, thread-local, incremented
  * once per launch decision of gemm_dev / the triangular solves (recursive calls count too; a product can count several routes:
  * the transposed orientation, split-K and a fused epilogue next to its kernel's tile).  faer_hip_debug_route_counts copies at
- * most `cap` counters in enum order and returns FaerHipRoute_Count. */
+ * most `cap` counters in enum order and returns FaerHipRoute_Count.  Values are stable: the slots of the in-place tiles, which
+ * no driver used and which were removed with their kernels, stay reserved. */
 typedef enum FaerHipRoute {
 	FaerHipRoute_GemmZeroK = 0,		/* K == 0: fill (Replace) or nothing (Add) */
 	FaerHipRoute_GemmRank1 = 1,		/* K == 1 stream */
@@ -708,8 +727,8 @@ typedef enum FaerHipRoute {
 	FaerHipRoute_GemmPipe64 = 6,		/* pipelined 64 x 64 tile */
 	FaerHipRoute_GemmPipe128 = 7,		/* pipelined 128 x 128 tile */
 	FaerHipRoute_GemmPipeWide = 8,		/* pipelined 128 x 256 tile (eight wavefronts) */
-	FaerHipRoute_GemmInplace32x128 = 9,	/* in-place product, 32 x 128 tile */
-	FaerHipRoute_GemmInplace128x32 = 10,	/* in-place product, 128 x 32 tile */
+	FaerHipRoute_Retired9 = 9,		/* retired (was the in-place product's 32 x 128 tile): reserved, always 0 */
+	FaerHipRoute_Retired10 = 10,		/* retired (was the in-place product's 128 x 32 tile): reserved, always 0 */
 	FaerHipRoute_GemmLegacy64 = 11,		/* non-pipelined 64 x 64 tile */
 	FaerHipRoute_GemmLegacy128 = 12,	/* non-pipelined 128 x 128 tile */
 	FaerHipRoute_GemmTriSkipSplit = 13,	/* tri_skip on operands the pipelined loaders cannot address: two plain products */

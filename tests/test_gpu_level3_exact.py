@@ -30,9 +30,10 @@ RANGE = {np.dtype(F32): 15, np.dtype(F64): 4095}
 
 # ------------------------------------------------------------------------------------------------ route counters
 # routes no direct call reaches: only the factorization drivers issue them (or nothing does), with the test that covers them
+# (slots of routes that were removed with their kernels stay in the enum, named Retired<slot>: they always count zero)
+RETIRED = [r for r in ROUTES if r.startswith("Retired")]
+LEVEL2_ROUTES = ("GemmZeroK", "GemmRank1", "GemmGemv", "GemmSkinny")
 DRIVER_ONLY = {
-    "GemmInplace32x128": "no driver sets GemmExtra::inplace at present; the in-place tiles have no caller to pin",
-    "GemmInplace128x32": "no driver sets GemmExtra::inplace at present; the in-place tiles have no caller to pin",
     "GemmTriSkipSplit": "tests.test_gpu_factor::test_llt_lookahead_on_a_view_with_reversed_rows_and_columns",
     "TrsmLeafPacked16": "tests.test_gpu_factor::test_llt_vs_oracle",
     "TrsmLeafPacked32": "tests.test_gpu_factor::test_llt_full_size_property",
@@ -248,6 +249,28 @@ def _nan_outside(t, s):
     return v
 
 
+def gemm_row_problem(dtype, row):
+    """the inputs of faer_hip_debug_gemm_plan (faer_rs_amd.GEMM_PLAN_INPUTS) for the library call test_gemm_route_is_exact makes
+    for a row of GEMM_ROWS: its shapes and options and the element strides of the operands the test builds (the test asserts
+    that its tensors have them).  No GPU needed."""
+    route, m, n, k, lay, acc, alpha, kind, extra, more = row
+    extras = dict(e.split(":") if ":" in e else (e, "") for e in extra.split("+") if e)
+    block = {"rect": 0, "lower": 1, "upper": 2, "strict_lower": 3, "strict_upper": 4, "unit_lower": 5, "unit_upper": 6}
+    indexed = "idx32" in extras or "idx64" in extras
+    dm, dn = (m + 250, n + 250) if indexed else (m, n)
+    ars, acs = (1, m) if lay[0] == "F" else (k, 1)
+    brs, bcs = (1, k) if lay[1] == "F" else (n, 1)
+    drs, dcs = (1, dm + 9) if "parent" in extras else (1, dm) if lay[2] == "F" else (dn, 1)
+    if "neg_strides" in extras:
+        ars, bcs = -ars, -bcs
+    if "huge_ld" in extras:
+        brs, bcs = 1, (1 << 31) // (256 * np.dtype(dtype).itemsize) + 1000
+    return dict(m=m, n=n, k=k, elem_bytes=np.dtype(dtype).itemsize, kind={"f": 0, "l": 1, "u": 2}[kind.replace("strict_", "")[0]],
+                add=int(acc == "add"), alpha_sign={1.0: 1, -1.0: -1}.get(alpha, 0), drs=drs, dcs=dcs, ars=ars, acs=acs, brs=brs, bcs=bcs,
+                indexed=int(indexed), diag=int("diag" in extras), a_struct=block[extras.get("astruct", "rect")],
+                b_struct=block[extras.get("bstruct", "rect")], variant=int(extras.get("variant", 0)))
+
+
 def _set_variant(F, v):
     F.lib().faer_hip_set_gemm_variant(C.c_int(v))
 
@@ -313,6 +336,8 @@ def test_gemm_route_is_exact(case):
     a_in, b_in = _nan_outside(a, astruct), _nan_outside(b, bstruct)
     accum = F.ACCUM_ADD if add else F.ACCUM_REPLACE
     variant = int(extras.get("variant", 0))
+    prob = gemm_row_problem(dtype, case[1:])
+    strides = {"d": tuple(dst.stride()), "a": tuple(a_in.stride()), "b": tuple(b_in.stride())}
     _set_variant(F, variant)
     try:
         with Routes(F) as rt:
@@ -324,6 +349,7 @@ def test_gemm_route_is_exact(case):
                 isz = sa.element_size()
                 va = F.MatRef(sa.data_ptr() + (m - 1) * sa.stride(0) * isz, m, k, -sa.stride(0), sa.stride(1))
                 vb = F.MatRef(sb.data_ptr() + (n - 1) * sb.stride(1) * isz, k, n, sb.stride(0), -sb.stride(1))
+                strides.update(a=(va.row_stride, va.col_stride), b=(vb.row_stride, vb.col_stride))
                 al = (C.c_double if dtype == F64 else C.c_float)(alpha)
                 getattr(F.lib(), f"libfaer_v0_23_matmul_{suffix(dtype)}")(F._mat(dst, F.MatMut), C.c_int(accum), va, vb, C.byref(al),
                                                                          F.PAR_SEQ)
@@ -334,6 +360,7 @@ def test_gemm_route_is_exact(case):
                 big[:, :k] = b.t()
                 vb = big[:, :k].t()
                 assert vb.stride() == (1, ld)
+                strides["b"] = tuple(vb.stride())
                 F.matmul(dst, accum, a_in, vb, alpha)
             else:
                 dk = {"full": F.DST_FULL, "lower": F.DST_LOWER, "upper": F.DST_UPPER}[kind]
@@ -341,6 +368,17 @@ def test_gemm_route_is_exact(case):
     finally:
         _set_variant(F, 0)
     rt.assert_hit(route, *more)
+    # what ran is what the dispatch plans for this call (faer_hip_debug_gemm_plan), no route more and none less; the level-2
+    # kernels decide for themselves and count their own route only
+    ran = {r for r, c in rt.hits.items() if c and r.startswith("Gemm")}
+    if route in LEVEL2_ROUTES:
+        assert ran == {route}, ran
+    else:
+        assert strides == {"d": (prob["drs"], prob["dcs"]), "a": (prob["ars"], prob["acs"]), "b": (prob["brs"], prob["bcs"])}, strides
+        plan = F.debug_gemm_plan(**prob)
+        assert isinstance(plan, dict), plan
+        assert ran == {r for i, r in enumerate(ROUTES) if plan["routes"] >> i & 1}, (ran, plan)
+    assert not any(rt.hits[r] for r in RETIRED)
     got = dst.double()
     exp = want.to(tdt).double()
     ok = (got == exp) | ~region
@@ -542,7 +580,10 @@ def test_case_tables_name_every_route():
         named.setdefault(r, set()).update(DTYPES)
     unknown = (set(named) | set(DRIVER_ONLY)) - set(ROUTES)
     assert not unknown, unknown
+    assert len(RETIRED) == 2 and not set(RETIRED) & (set(named) | set(DRIVER_ONLY))
     for r in ROUTES:
+        if r in RETIRED:
+            continue
         if r in DRIVER_ONLY:
             assert r not in named, f"{r} is pinned here: drop it from DRIVER_ONLY"
             why = DRIVER_ONLY[r]
