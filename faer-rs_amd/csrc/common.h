@@ -117,7 +117,12 @@ struct Ctx {
 	void sync() { FH_HIP(hipStreamSynchronize(stream)); }
 	void set_stream(hipStream_t s); // the caller's stream (faer_hip_set_stream); internal code switches `stream` directly
 	// after a point where every internal stream has been joined AND the caller's stream synchronised: free
-	// buffers may be handed to any stream again
+	// buffers last used on these streams may be handed to any stream again (those of other caller streams keep their owner).
+	// What that costs: a free buffer whose owner is a caller stream that was still busy when set_stream() left it is not polled
+	// again (alloc() polls the library's own streams and the null stream only, set_stream() the stream it leaves -- a stream the
+	// caller may have destroyed must not be queried); it is reused when the caller returns to that stream, else it stays in the pool
+	// until a failed hipMalloc purges the free buffers.  A caller cycling through short-lived streams with work in flight grows
+	// the pool by up to one set of buffers per stream.
 	void quiesce();
 };
 Ctx &ctx();

@@ -432,9 +432,13 @@ void Ctx::set_stream(hipStream_t s)
 
 void Ctx::quiesce()
 {
-	for (auto &b : pool)
-		if (!b.used)
+	// only what the synchronised stream and the library's own streams (joined into it) used last: a free buffer whose owner is
+	// ANOTHER stream of the caller (faer_hip_set_stream) may still be read or written by work queued there
+	for (auto &b : pool) {
+		const bool internal = (la_state > 0 && (b.owner == la_bulk || b.owner == la_panel)) || (qr_side[0] && b.owner == qr_side[0]);
+		if (!b.used && (b.owner == stream || internal))
 			b.owner = ANY_STREAM;
+	}
 }
 
 void Ctx::release(void *p)

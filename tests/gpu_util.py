@@ -1,4 +1,5 @@
 """helpers shared by the -m gpu parity tests (device tensors are column major like faer::Mat)."""
+import contextlib
 import ctypes as C
 import os
 import re
@@ -219,3 +220,113 @@ class Routes:
     def assert_hit(self, *names):
         missing = [r for r in names if self.hits[r] <= 0]
         assert not missing, (missing, {k: v for k, v in self.hits.items() if v})
+
+
+# ---- a non-blocking caller stream and the ordering protocol of tests/test_gpu_stream_order.py
+DELAY_PRODUCTS = 12  # 4096^3 fp64 products of delay(): about 1.9 ms each at the README's 72 TFLOP/s; sized by the module's control
+_DELAY_OPERANDS = []
+
+
+@contextlib.contextmanager
+def on_stream(S):
+    """torch's current stream and the library's stream are the non-blocking `S` inside, the default stream again afterwards"""
+    import torch
+
+    F = fa()
+    assert S.cuda_stream != 0
+    try:
+        with torch.cuda.stream(S):
+            F.use_torch_stream()
+            yield S
+    finally:
+        F.use_torch_stream()  # (torch is back on its default stream here)
+
+
+def delay_operands():
+    """the operands of delay(), allocated and filled on the default stream: call it before the host wait that precedes delay()"""
+    import torch
+
+    if not _DELAY_OPERANDS:
+        g = torch.Generator(device="cuda").manual_seed(1)
+        _DELAY_OPERANDS.extend(torch.rand((4096, 4096), dtype=torch.float64, device="cuda", generator=g).t() for _ in range(2))
+        _DELAY_OPERANDS.append(torch.zeros((4096, 4096), dtype=torch.float64, device="cuda").t())
+    return _DELAY_OPERANDS
+
+
+def delay(S, products=DELAY_PRODUCTS):
+    """keeps `S` busy with the library's own DGEMM (inside on_stream(S)); the host does not wait"""
+    import torch
+
+    F = fa()
+    assert _DELAY_OPERANDS, "delay_operands() first"
+    assert torch.cuda.current_stream() == S and F.lib().faer_hip_get_stream() == S.cuda_stream
+    a, b, c = _DELAY_OPERANDS
+    for _ in range(products):
+        F.matmul(c, F.ACCUM_REPLACE, a, b, 1.0)
+
+
+def _fresh(src):
+    """device copies with the memory order of the source (a C-contiguous numpy matrix stays row major)"""
+    def one(v):
+        if not isinstance(v, np.ndarray):
+            return v.clone()
+        return to_dev(v, "C" if v.flags.c_contiguous and not v.flags.f_contiguous else "F")
+
+    return {k: one(v) for k, v in src.items()}
+
+
+def _host(out):
+    import torch
+
+    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else v) for k, v in out.items()}
+
+
+def ordered_call(fn, inputs_good, inputs_stale, S=None, products=DELAY_PRODUCTS, routes=()):
+    """`fn(bufs)` runs public calls on the device tensors `bufs` (one per entry of the inputs: numpy arrays or device tensors of the
+    same shapes) and returns {name: device tensor or host value}.  Returns (expected, got) as host values:
+    expected -- fn on fresh copies of inputs_good on the default stream, synchronised;
+    got      -- the working buffers hold inputs_stale; then on the non-blocking stream S, with no host synchronisation in between:
+                delay, the copy of inputs_good into the buffers (the producer), fn, a copy of every output tensor (the consumer);
+                the host waits for S alone.
+    A call that starts before the producer factors the stale matrix; a call whose internal streams have not been joined into S
+    when it returns leaves unfinished outputs to the consumer.  `routes`: dispatch routes the expected run must hit."""
+    import torch
+
+    F = fa()
+    assert inputs_good.keys() == inputs_stale.keys()
+    with Routes(F) as r:
+        first = fn(_fresh(inputs_good))
+    r.assert_hit(*routes)  # the GEMM / TRSM dispatch routes the case is about (the same inputs take them again on S)
+    expected = _host(first)
+    good, bufs = _fresh(inputs_good), _fresh(inputs_stale)
+    snaps = {k: torch.empty_like(v) for k, v in first.items() if torch.is_tensor(v)}
+    delay_operands()
+    S = S or torch.cuda.Stream()
+    torch.cuda.synchronize()  # S is non-blocking: it would not wait for the fills above
+    with on_stream(S):
+        delay(S, products)
+        for k in bufs:
+            bufs[k].copy_(good[k], non_blocking=True)
+        out = fn(bufs)
+        for k in snaps:
+            snaps[k].copy_(out[k], non_blocking=True)
+    S.synchronize()  # that stream only
+    got = _host({k: (snaps[k] if k in snaps else v) for k, v in out.items()})
+    del first, good, bufs, snaps, out  # (alive until here: allocated on the default stream, used on S)
+    return expected, got
+
+
+def same_result(expected, got, what=""):
+    """every entry bit for bit (floating point) or exactly (indices, counts, status)"""
+    assert expected.keys() == got.keys(), (what, sorted(expected), sorted(got))
+    for k, e in expected.items():
+        g = got[k]
+        if isinstance(e, np.ndarray):
+            assert e.dtype == g.dtype and e.shape == g.shape, (what, k)
+            if e.dtype.kind == "f":
+                ne = bits(np.ascontiguousarray(e)) != bits(np.ascontiguousarray(g))
+                assert not ne.any(), (what, k, f"{int(ne.sum())} of {ne.size} entries differ; first at {tuple(np.argwhere(ne)[0])}")
+            else:
+                assert np.array_equal(e, g), (what, k)
+        else:
+            assert e == g, (what, k, e, g)
