@@ -300,7 +300,9 @@ static __device__ __forceinline__ bool qr2_step(const QrPanelArgs<T> &a, T (&x)[
 	T kc[QR_PW];
 #pragma unroll
 	for (int c = 0; c < QR_PW; ++c)
-		kc[c] = (c > J && c < w) ? -(((T) sh.head[c] + hinv * (T) sh.S[c]) * tau_inv) : (T) 0;
+		// (sh.S[c] = x_J^H a_c carries the SQUARE of the data's scale: outside the range of fp32 for entries beyond 2^+-63 although
+		// v^H a_c = hinv * S[c] is not -- the product is formed in fp64 before it is rounded to T; unchanged for T = double)
+		kc[c] = (c > J && c < w) ? -(((T) sh.head[c] + (T) ((double) hinv * sh.S[c])) * tau_inv) : (T) 0;
 #pragma unroll
 	for (int i = 0; i < RPT; ++i) {
 		const int gr = r0 + tid + i * QR2_NT;

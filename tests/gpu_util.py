@@ -55,6 +55,33 @@ def spd(rng, n, dtype=np.float64):
     return np.asarray(a @ a.T + n * np.eye(n), dtype=dtype, order="F")
 
 
+def sym(rng, n, dtype):
+    a = rng.standard_normal((n, n))
+    return np.asarray(a + a.T, dtype=dtype, order="F")
+
+
+def well_conditioned(rng, n, dtype):
+    return np.asarray(rng.standard_normal((n, n)) + 2 * np.sqrt(n) * np.eye(n), dtype=dtype, order="F")
+
+
+def quasi_definite(rng, n, dtype=np.float64):
+    n1 = n // 2
+    h = rng.standard_normal((n, n))
+    H = h[:n1, :n1] @ h[:n1, :n1].T + n * np.eye(n1)
+    G = h[n1:, n1:] @ h[n1:, n1:].T + n * np.eye(n - n1)
+    B = h[n1:, :n1]
+    return np.asarray(np.block([[H, B.T], [B, -G]]), dtype=dtype, order="F"), n1
+
+
+def boosted(n):
+    """positive definite with its largest diagonal entry at index 0, so that step 0 of a diagonally pivoted factorization does not swap"""
+    import piv_llt_ref
+
+    a = piv_llt_ref.spd(n, 3 + n)
+    a[0, 0] = 2 * np.diag(a).max()
+    return a
+
+
 # ---- bit patterns (NaN payloads and signed zeros compare as what they are)
 def bits(t):
     """the elements of a torch tensor or numpy array as integers of the same width"""

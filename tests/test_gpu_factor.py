@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from gpu_util import EPS, Routes, init_gpu, rnd, spd, to_dev, to_host
+from gpu_util import quasi_definite as _quasi_definite
 
 pytestmark = pytest.mark.gpu
 
@@ -733,15 +734,6 @@ def test_plu_solve_and_transpose_solve(n, k, dtype):
 
 
 # -------------------------------------------------------------------------------------------- ldlt
-def _quasi_definite(rng, n, dtype=np.float64):
-    n1 = n // 2
-    h = rng.standard_normal((n, n))
-    H = h[:n1, :n1] @ h[:n1, :n1].T + n * np.eye(n1)
-    G = h[n1:, n1:] @ h[n1:, n1:].T + n * np.eye(n - n1)
-    B = h[n1:, :n1]
-    return np.asarray(np.block([[H, B.T], [B, -G]]), dtype=dtype, order="F"), n1
-
-
 @pytest.mark.parametrize("n", [1, 2, 31, 32, 33, 127, 128, 129, 257, 640, 1100])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_ldlt_vs_oracle(oracle, n, dtype):

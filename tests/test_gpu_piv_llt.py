@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import piv_llt_ref as ref
-from gpu_util import EPS, guard_intact, init_gpu, place, same_bits, to_dev, to_host, view_box
+from gpu_util import EPS, boosted, guard_intact, init_gpu, place, same_bits, to_dev, to_host, view_box
 
 pytestmark = pytest.mark.gpu
 GOLDEN = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "piv_llt_cases.json")))
@@ -176,13 +176,6 @@ def test_pivot_parity_low_rank(n):
     print("residual", res, "bound", tol(n, np.float64) * np.abs(a).max())
     assert res <= tol(n, np.float64) * np.abs(a).max()
     assert r["last"][2] == rank and r["last"][3] == 0
-
-
-def boosted(n):
-    """positive definite with its largest diagonal entry at index 0, so that step 0 does not swap"""
-    a = ref.spd(n, 3 + n)
-    a[0, 0] = 2 * np.diag(a).max()
-    return a
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -494,6 +494,15 @@ def test_qr_norm_l2_scaling_cases(oracle, m, n, factor):
     bs = max(1, min(F.qr_recommended_block_size(m, n), size))
     dqr, dh = to_dev(a), to_dev(np.zeros((bs, size)))
     rank = F.qr_factor_in_place(dqr, dh)
+    if (m, n) == (3000, 40):
+        # which path this case tests: 3000 x 40 is inside the whole-matrix one-pass rule, whose range guard (tsqr.hip TqLim<double>: mean square of
+        # every column within [1e-200, 1e200]) keeps the factors 1e+-30 and hands every other factor to the classic path before a column is done
+        F.lib().faer_hip_debug_qr_one_pass_columns.restype = C.c_long
+        with np.errstate(over="ignore", under="ignore"):
+            sq = np.square(a).sum(axis=0)
+        inside = bool(((sq >= 1e-200 * m) & (sq <= 1e200 * m)).all())
+        assert inside == (factor in (1e30, 1e-30))
+        assert F.lib().faer_hip_debug_qr_one_pass_columns() == (n if inside else 0)
     qr, h = to_host(dqr), to_host(dh)
     ref, rh = a.copy(order="F"), np.zeros((bs, size), order="F")
     assert oracle.qr_in_place(ref, rh) == size and rank == size

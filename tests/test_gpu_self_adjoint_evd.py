@@ -294,3 +294,27 @@ def test_runs_inside_gap_segments(n, dtype, step):
         tag, s, u = run(F, a, prm=params(F, dtype, rt))
         assert tag == F.EVD_OK
         check(a, s, u)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rt", [4, 128])
+@pytest.mark.parametrize("n", [130, 300])
+def test_scaled_to_the_ends_of_the_range(n, rt, dtype):
+    """A * 2^k over the table of tests/range_cases.py (fp64 to 2^+-900, beyond the 1e+-150 of the deflation cases; fp32 to 2^-90 / 2^100,
+    where its dnc_scale_kernel / dnc_tscale_kernel rescaling and the fp32 norm accumulators leave the safe range for the first time);
+    n = 130: two leaves and one merge.  With vectors and values only; `check` is relative to ||A||."""
+    import range_cases as rc
+
+    F = init_gpu()
+    a0 = sym(np.random.default_rng(n + 7), n, dtype)
+    for k in rc.K["evd"][np.dtype(dtype)]:
+        a = rc.scaled(a0, k)
+        assert rc.cap_ok(a)
+        for with_u in (True, False):
+            tag, s, u = run(F, a, with_u=with_u, prm=params(F, dtype, rt))
+            assert tag == F.EVD_OK, (k, with_u)
+            assert rc.cap_ok(s), (k, with_u)
+            try:  # `check` is relative to ||A|| but squares residuals on the way (inf at 2^900, 0 at 2^-900): it gets A and S times 2^-k, exactly
+                check(a0, rc.unscale(s, k, 1), u)
+            except AssertionError as e:
+                raise AssertionError(f"2^{k}, vectors {with_u}: {e}") from None

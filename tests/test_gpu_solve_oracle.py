@@ -8,13 +8,9 @@ Both sides run the same algorithm on factors that agree to c n eps kappa, so the
 import numpy as np
 import pytest
 
-from gpu_util import EPS, init_gpu, rnd, spd, to_dev, to_host
+from gpu_util import EPS, init_gpu, rnd, spd, to_dev, to_host, well_conditioned
 
 pytestmark = pytest.mark.gpu
-
-
-def well_conditioned(rng, n, dtype):
-    return np.asarray(rng.standard_normal((n, n)) + 2 * np.sqrt(n) * np.eye(n), dtype=dtype, order="F")
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

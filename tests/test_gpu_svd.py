@@ -353,3 +353,27 @@ def test_size_2048_f64():
     tag, s, u, v = run(F, a)
     assert tag == F.SVD_OK
     check(a, s, u, v)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rt", [4, 128])
+@pytest.mark.parametrize("n", [130, 300])
+def test_scaled_to_the_ends_of_the_range(n, rt, dtype):
+    """A * 2^k over the table of tests/range_cases.py (fp64 to 2^+-900, beyond the 1e+-150 of the deflation cases; fp32 to 2^-90 / 2^100,
+    outside the safe range of plain fp32 sums of squares); n = 130: two leaves and one merge.  With vectors and values only; `check` is
+    relative to ||A||."""
+    import range_cases as rc
+
+    F = init_gpu()
+    a0 = rand(n + 7, n, n, dtype)
+    for k in rc.K["svd"][np.dtype(dtype)]:
+        a = rc.scaled(a0, k)
+        assert rc.cap_ok(a)
+        for mode in ("thin", "no"):
+            tag, s, u, v = run(F, a, mode, mode, prm=params(F, dtype, recursion_threshold=rt))
+            assert tag == F.SVD_OK, (k, mode)
+            assert rc.cap_ok(s), (k, mode)
+            try:  # `check` is relative to ||A||: it gets A and S times 2^-k, exactly, so that nothing it squares leaves the range of fp64
+                check(a0, rc.unscale(s, k, 1), u, v)
+            except AssertionError as e:
+                raise AssertionError(f"2^{k}, vectors {mode}: {e}") from None

@@ -3,16 +3,11 @@ restatement of faer/src/linalg/evd/tridiag.rs:274-535 and the reference's own pr
 import numpy as np
 import pytest
 
-from gpu_util import EPS, init_gpu, to_dev, to_host
+from gpu_util import EPS, init_gpu, sym, to_dev, to_host
 from oracle import oracle as O
 from test_tridiag_oracle import qh_a_q, tridiag_of
 
 pytestmark = pytest.mark.gpu
-
-
-def sym(rng, n, dtype):
-    a = rng.standard_normal((n, n))
-    return np.asarray(a + a.T, dtype=dtype, order="F")
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
