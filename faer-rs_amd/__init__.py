@@ -242,6 +242,7 @@ def lib():
     L.libfaer_v0_23_get_global_par.restype = Par
     L.faer_hip_version.restype = C.c_char_p
     L.faer_hip_device_count.restype = C.c_int
+    L.faer_hip_lblt_pivoting_supported.restype = C.c_int
     L.faer_hip_get_stream.restype = C.c_void_p
     L.faer_hip_malloc.restype = C.c_void_p
     L.faer_hip_time_gemm_ms.restype = C.c_double
@@ -1022,8 +1023,9 @@ def _vec(x, cls=VecRef):
 def lblt_factor_in_place(a, subdiag=None, pivoting=None, index_dtype=np.uint64, par=PAR_SEQ):
     """cholesky/bunch_kaufman/factor.rs:1161-1234: P A P^T = L B L^T of the symmetric matrix in the lower triangle of `a` (the strict
     upper triangle is never touched).  Unit lower L strictly below the diagonal of `a`, the diagonal of B on it, the subdiagonal of
-    the 2 x 2 blocks in `subdiag` (created next to `a` when None).  pivoting: a PIVOTING_* constant (None: the default, PartialDiag).
-    returns (subdiag, perm_fwd, perm_bwd, transposition_count)"""
+    the 2 x 2 blocks in `subdiag` (created next to `a` when None).  pivoting: a PIVOTING_* constant or a key of PivotingStrategy
+    ("partial", ..., "full"; None: the default, PartialDiag).  A value the library does not run raises ValueError (the C entry point
+    would abort).  returns (subdiag, perm_fwd, perm_bwd, transposition_count)"""
     suf, _, _ = _dtype_suffix(a)
     n = a.shape[0]
     it = "u64" if np.dtype(index_dtype) == np.uint64 else "u32"
@@ -1039,12 +1041,21 @@ def lblt_factor_in_place(a, subdiag=None, pivoting=None, index_dtype=np.uint64, 
     L = lib()
     params = getattr(L, f"libfaer_v0_23_LbltParams_{suf}")()
     if pivoting is not None:
-        params.pivoting = int(pivoting)
+        params.pivoting = PivotingStrategy[pivoting] if isinstance(pivoting, str) else int(pivoting)
+        if not lblt_pivoting_supported(params.pivoting):
+            raise ValueError(f"lblt_factor_in_place: unsupported pivoting strategy {pivoting!r}")
     st = getattr(L, f"libfaer_v0_23_lblt_factor_in_place_{it}_{suf}")(
         _mat(a, MatMut), _vec(subdiag, VecMut), SliceMut(fwd.ctypes.data, n), SliceMut(bwd.ctypes.data, n), par, MemAlloc(None, 0), params)
     if st.tag != 0:
         raise RuntimeError("LbltStatus::Unknown")
     return subdiag, fwd, bwd, st.transposition_count
+
+
+def lblt_pivoting_supported(pivoting):
+    """1 if lblt_factor_in_place runs the FaerPivotingStrategy value `pivoting` (an int or a key of PivotingStrategy), else 0; no GPU call"""
+    if isinstance(pivoting, str):
+        pivoting = PivotingStrategy.get(pivoting, -1)
+    return int(lib().faer_hip_lblt_pivoting_supported(C.c_int(int(pivoting))))
 
 
 def _lblt_call(name, lb, diag, subdiag, perm_fwd, perm_bwd):
@@ -1077,7 +1088,9 @@ def lblt_inverse(out, lb, subdiag, perm_fwd, perm_bwd, diag=None, par=PAR_SEQ):
 
 
 def debug_lblt_last():
-    """(blocked panels, leaf rows, 2 x 2 pivots, host synchronisations inside panels) of this thread's last lblt_factor_in_place"""
+    """(blocked panels, leaf rows, 2 x 2 pivots, host synchronisations inside panels) of this thread's last lblt_factor_in_place;
+    for the Full strategy (pivot steps of the multi-workgroup path, rows finished by the leaf, 2 x 2 pivots, host synchronisations
+    before the leaf)"""
     out = (C.c_size_t * 4)()
     lib().faer_hip_debug_lblt_last(out)
     return tuple(int(v) for v in out)
@@ -1215,7 +1228,8 @@ class Llt:
 
 
 class Lblt:
-    """solvers.rs Lblt: copies the matrix, factors its lower triangle with the default strategy"""
+    """solvers.rs Lblt: copies the matrix, factors its lower triangle with the default strategy, or with `pivoting` (as
+    lblt_factor_in_place takes it)"""
 
     def __init__(self, a, pivoting=None):
         self.lb = _copy_f(a)

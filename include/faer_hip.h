@@ -540,11 +540,25 @@ FAER_HIP_API FaerSvdStatus libfaer_v0_23_svd_f32(FaerMatRef A, FaerMatMut U, Fae
  *     block.  perm_fwd[i] = source index of row i of P A P^T, perm_bwd its inverse (HOST memory, dim entries);
  *     transposition_count = number of positions whose pivot index differs from the position.  Pivoting strategies
  *     Partial, PartialDiag (the default), Rook and RookDiag follow the reference's decision tree, ties of every arg-max
- *     going to the lowest index.  Full is a different level-2 algorithm and is NOT implemented: it aborts with a message
- *     naming the strategy (the boundary's convention for unsupported input).  params.block_size and par_threshold are
+ *     going to the lowest index.  A value of params.pivoting outside the enum aborts with a message naming it (the
+ *     boundary's convention for unsupported input); faer_hip_lblt_pivoting_supported (section 3) asks instead.
+ *     params.block_size and par_threshold are
  *     hints and ignored: the GPU factors panels of 64 columns by the lazily updated W-panel algorithm and the last <= 64
  *     rows in one LDS-resident workgroup (csrc/lblt.hip); the pivot sequence does not depend on the blocking in exact
- *     arithmetic.  solve / reconstruct / inverse take L and the strided `diag` and `subdiag` vectors as the factorization
+ *     arithmetic.
+ *     Full (factor.rs:264-429, lblt_full_piv) is a level-2 algorithm of its own: the lower triangle is multiplied by the
+ *     reciprocal of its largest magnitude; every step takes the first largest diagonal entry of the trailing matrix as a
+ *     1 x 1 pivot if its square is >= ((1 + sqrt 17) / 8)^2 times the largest squared off-diagonal entry (ties: lowest
+ *     column, then lowest row), else that off-diagonal entry as a 2 x 2 pivot; once the trailing off-diagonal is zero the
+ *     remaining diagonal is only ordered by decreasing magnitude; at the end the diagonal and subdiag are multiplied by
+ *     the scale (L has none).  Three deliberate deviations from the reference: (1) the reference takes the largest
+ *     magnitude of the whole matrix, scales the whole matrix and leaves its strict upper triangle scaled; here the strict
+ *     upper triangle is neither read nor written, as for every strategy -- for a symmetric input the lower triangle,
+ *     subdiag and the permutations are the same; (2) for the zero matrix the reference forms 0 * inf; here both scalings
+ *     are skipped and the result is the input unchanged, zero subdiag, identity permutation, count 0; (3) for non-finite
+ *     input, and for a scale whose reciprocal overflows, the call returns Ok, terminates and writes only inside the lower
+ *     triangle; nothing is promised about the values.
+ *     solve / reconstruct / inverse take L and the strided `diag` and `subdiag` vectors as the factorization
  *     leaves them; reconstruct writes the lower triangle of A only, inverse the whole of A_inv.  Host or device operands,
  *     any strides; par, mem and A_conj are accepted and ignored.  The scratch queries need no device.
  * --------------------------------------------------------------------------------------------- */
@@ -653,6 +667,9 @@ FAER_HIP_API void faer_hip_synchronize(void);
 /* Releases the calling thread's internal look-ahead streams and events (they are re-created on demand).
  * Call before unloading the library or at process exit. */
 FAER_HIP_API void faer_hip_shutdown(void);
+/* 1 if libfaer_v0_23_lblt_factor_in_place_* runs `pivoting` (the five values of FaerPivotingStrategy), 0 for any other value, which
+ * that entry point would abort on.  Makes no GPU call and creates no context. */
+FAER_HIP_API int faer_hip_lblt_pivoting_supported(FaerPivotingStrategy pivoting);
 /* Device memory helpers for C clients without another allocator. */
 FAER_HIP_API void *faer_hip_malloc(size_t bytes);
 FAER_HIP_API void faer_hip_free(void *ptr);
@@ -695,7 +712,9 @@ FAER_HIP_API size_t faer_hip_debug_llt_plan(size_t n, size_t tail_rows, size_t n
 FAER_HIP_API size_t faer_hip_debug_llt_steps(size_t n, size_t la_min, size_t tail_rows, size_t side_rmin, size_t dpanel_rmin, int *codes,
 					     size_t cap);
 /* tests: the calling thread's last lblt_factor_in_place -- out = {blocked panels, rows handled by the leaf, 2 x 2 pivots, host
- * synchronisations made inside panels (0 for Partial / PartialDiag; one per rook iteration for Rook / RookDiag)} */
+ * synchronisations made inside panels (0 for Partial / PartialDiag; one per rook iteration for Rook / RookDiag)}.
+ * For the Full strategy: out[0] = pivot steps run by the multi-workgroup path, out[1] = rows finished by the leaf,
+ * out[2] = number of 2 x 2 pivots, out[3] = host synchronisations before the leaf (at most one per 64 launched steps). */
 FAER_HIP_API void faer_hip_debug_lblt_last(size_t out[4]);
 /* tests: the calling thread's last piv_llt_factor_in_place -- out = {blocked panels, rows handled by the leaf (0: the factorization
  * ended in a panel), columns of L factored (the rank), host synchronisations made inside panels (0)} */
