@@ -158,6 +158,27 @@ class EvdStatus(C.Structure):
 
 EVD_OK, EVD_NO_CONVERGENCE = 0, 1
 
+SHIFT_FN = C.CFUNCTYPE(C.c_size_t, C.c_size_t, C.c_size_t)
+
+
+class HessenbergParams(C.Structure):
+    _fields_ = [("par_threshold", C.c_size_t), ("blocking_threshold", C.c_size_t)]
+
+
+class SchurParams(C.Structure):
+    """include/faer_hip.h FaerSchurParams: two function pointers (matrix dimension, active block dimension) -> size_t, two sizes"""
+    _fields_ = [("recommended_shift_count", SHIFT_FN), ("recommended_deflation_window", SHIFT_FN),
+                ("blocking_threshold", C.c_size_t), ("nibble_threshold", C.c_size_t)]
+
+
+class EvdFromSchurParams(C.Structure):
+    _fields_ = [("recursion_threshold", C.c_size_t)]
+
+
+class EvdParams(C.Structure):
+    """include/faer_hip.h FaerEvdParams {hessenberg, schur, evd_from_schur}"""
+    _fields_ = [("hessenberg", HessenbergParams), ("schur", SchurParams), ("evd_from_schur", EvdFromSchurParams)]
+
 
 class BidiagParams(C.Structure):
     _fields_ = [("par_threshold", C.c_size_t)]
@@ -557,6 +578,40 @@ def self_adjoint_evd(a, s, u=None, params=None, par=PAR_SEQ):
     fn.restype = EvdStatus
     st = fn(_mat(a), um, sv, par, MemAlloc(None, 0), params)
     return st.tag
+
+
+def evd(a, s, s_im, ul=None, ur=None, params=None, par=PAR_SEQ):
+    """faer::linalg::evd::evd_real (evd/mod.rs:1213): eigenvalues of the general real `a` (n x n, never written), real parts
+    into the 1-D `s`, imaginary parts into `s_im`; with `ul` / `ur` (n x n) the left / right eigenvectors in the reference's
+    packed layout (a real eigenvalue: column i; a pair at (i, i + 1): real part, imaginary part).  Returns the status tag
+    (EVD_OK or EVD_NO_CONVERGENCE)."""
+    suf, _, _ = _dtype_suffix(a)
+    L = lib()
+    if params is None:
+        pf = getattr(L, f"libfaer_v0_23_EvdParams_{suf}")
+        pf.restype = EvdParams
+        params = pf()
+    n = a.shape[0]
+    ulm = _mat(ul, MatMut) if ul is not None else MatMut(None, n, 0, 1, n)
+    urm = _mat(ur, MatMut) if ur is not None else MatMut(None, n, 0, 1, n)
+    fn = getattr(L, f"libfaer_v0_23_evd_{suf}")
+    fn.restype = EvdStatus
+    st = fn(_mat(a), ulm, urm, _vec(s, VecMut), _vec(s_im, VecMut), par, MemAlloc(None, 0), params)
+    return st.tag
+
+
+def debug_evd_last_counts():
+    """{sweeps, window steps, leaf launches, state read-backs} of the calling thread's last evd"""
+    out = (C.c_long * 4)()
+    lib().faer_hip_debug_evd_last_counts(out)
+    return dict(zip(("sweeps", "window_steps", "leaves", "readbacks"), (int(v) for v in out)))
+
+
+def evd_window_edge(dtype):
+    """W: the edge of the LDS-resident window of the Schur kernels (96 for float64, 128 for float32)"""
+    f = lib().faer_hip_evd_window_edge
+    f.restype = C.c_size_t
+    return int(f(C.c_int(DTYPE_F64 if np.dtype(dtype) == np.float64 else DTYPE_F32)))
 
 
 def svd(a, s, u=None, v=None, params=None, par=PAR_SEQ):

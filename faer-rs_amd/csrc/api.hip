@@ -3,6 +3,7 @@
 // to the device drivers; there is deliberately no CPU compute path here.
 #include <atomic>
 
+#include "arena.h"
 #include "common.h"
 #include "perm.h"
 
@@ -622,6 +623,56 @@ void colpiv_qr_inverse_api(FaerMatMut Out, FaerMatRef Qb, FaerMatRef Qc, FaerMat
 }
 
 // evd/mod.rs:270-425 behind lib.rs:2385-2399 (U.ncols == 0: no eigenvectors)
+// evd/mod.rs:1213 evd_real.  All device memory of the call -- the working matrices of evd_dev and the staged images of host
+// operands -- is one arena (arena.h).
+template <typename T> FaerEvdStatus evd_api(FaerMatRef A, FaerMatMut UL, FaerMatMut UR, FaerVecMut S, FaerVecMut S_im, FaerEvdParams params)
+{
+	const size_t n = A.nrows;
+	FH_CHECK(A.ncols == n && S.len == n && S_im.len == n, "evd: A must be square, S and S_im must have n entries"); // mod.rs:1224
+	FH_CHECK(UL.ncols == 0 || (UL.nrows == n && UL.ncols == n), "evd: UL must be n x n (or have no columns)");
+	FH_CHECK(UR.ncols == 0 || (UR.nrows == n && UR.ncols == n), "evd: UR must be n x n (or have no columns)");
+	FH_CHECK(params.schur.recommended_shift_count != nullptr, "evd: params.schur.recommended_shift_count is NULL");
+	FaerEvdStatus st;
+	memset(&st, 0, sizeof(st));
+	st.tag = FaerEvdStatus_Ok;
+	if (n == 0)
+		return st; // mod.rs:1018
+	ctx().ensure_device();
+	const bool want_l = UL.ncols != 0, want_r = UR.ncols != 0;
+	const idx_t N = (idx_t) n, bs = (idx_t) qr_block_size(n - 1, n - 1);
+	const MatV<const T> a = view<T>(A);
+	const MatV<T> ul = view<T>(UL), ur = view<T>(UR), s = vview<T>(S), si = vview<T>(S_im);
+	const bool a_host = !is_device_ptr(a.p), ul_host = want_l && !is_device_ptr(ul.p), ur_host = want_r && !is_device_ptr(ur.p);
+	const size_t nn = Arena::padded(n * n * sizeof(T));
+	int r;
+	{
+		Arena ar(evd_arena_bytes(N, want_l || want_r, bs < 1 ? 1 : bs, (int) sizeof(T)) + (size_t) ul_host * nn + (size_t) ur_host * nn + 512);
+		T *wr = ar.take<T>(n), *wi = ar.take<T>(n);
+		const MatV<T> dl = ul_host ? ar.mat<T>(N, N) : (want_l ? ul : MatV<T>{nullptr, N, N, 1, N});
+		const MatV<T> dr = ur_host ? ar.mat<T>(N, N) : (want_r ? ur : MatV<T>{nullptr, N, N, 1, N});
+		const MatV<const T> da = a_host ? ar.copy_in<T>(a).c() : a;
+		r = evd_dev<T>(ar, da, a_host, dl, dr, wr, wi, bs < 1 ? 1 : bs, params.schur.recommended_shift_count);
+		if (r == 0) {
+			const MatV<const T> wrv{wr, N, 1, 1, N}, wiv{wi, N, 1, 1, N};
+			if (is_device_ptr(s.p))
+				copy_dev<T>(s, wrv);
+			else
+				Arena::copy_out<T>(s, wrv);
+			if (is_device_ptr(si.p))
+				copy_dev<T>(si, wiv);
+			else
+				Arena::copy_out<T>(si, wiv);
+			if (ul_host)
+				Arena::copy_out<T>(ul, dl.c());
+			if (ur_host)
+				Arena::copy_out<T>(ur, dr.c());
+			ctx().sync();
+		}
+	}
+	st.tag = r == 0 ? FaerEvdStatus_Ok : FaerEvdStatus_NoConvergence;
+	return st;
+}
+
 template <typename T> FaerEvdStatus self_adjoint_evd_api(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerSelfAdjointEvdParams params)
 {
 	const size_t n = A.nrows;
@@ -1496,6 +1547,60 @@ FH_FOR_DTYPES(X)
 		(void) par;                                                                                            \
 		(void) mem;                                                                                            \
 		return svd_api<T>(A, U, S, V, params);                                                                 \
+	}
+FH_FOR_DTYPES(X)
+#undef X
+
+size_t faer_hip_default_recommended_shift_count(size_t n, size_t active)
+{
+	(void) active; // evd/schur/mod.rs:59-79
+	return n < 30 ? 2 : n < 60 ? 4 : n < 150 ? 12 : n < 590 ? 32 : n < 3000 ? 64 : n < 6000 ? 128 : 256;
+}
+size_t faer_hip_default_recommended_deflation_window(size_t n, size_t active)
+{
+	(void) active; // evd/schur/mod.rs:80-107
+	if (n < 30)
+		return 2;
+	if (n < 60)
+		return 4;
+	if (n < 150)
+		return 10;
+	if (n < 590)
+		return (size_t) ((double) n / log2((double) n));
+	return n < 3000 ? 96 : n < 6000 ? 192 : 384;
+}
+void faer_hip_debug_evd_last_counts(long out[4]) { evd_last_counts(out); }
+size_t faer_hip_evd_window_edge(FaerHipDType dtype) { return (size_t) schur_window_edge(dtype == FaerHipDType_F64 ? 8 : 4); }
+
+#define X(suf, T)                                                                                                      \
+	FaerHessenbergParams libfaer_v0_23_HessenbergParams_##suf(void) { return FaerHessenbergParams{192 * 256, 256 * 256}; } \
+	FaerSchurParams libfaer_v0_23_SchurParams_##suf(void)                                                          \
+	{                                                                                                              \
+		return FaerSchurParams{faer_hip_default_recommended_shift_count, faer_hip_default_recommended_deflation_window, 75, 50}; \
+	}                                                                                                              \
+	FaerEvdFromSchurParams libfaer_v0_23_EvdFromSchurParams_##suf(void) { return FaerEvdFromSchurParams{64}; }      \
+	FaerEvdParams libfaer_v0_23_EvdParams_##suf(void)                                                              \
+	{                                                                                                              \
+		return FaerEvdParams{libfaer_v0_23_HessenbergParams_##suf(), libfaer_v0_23_SchurParams_##suf(),        \
+				     libfaer_v0_23_EvdFromSchurParams_##suf()};                                        \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_evd_scratch_##suf(size_t dim, FaerComputeEigenvectors compute_left,                   \
+						   FaerComputeEigenvectors compute_right, FaerPar par, FaerEvdParams params) \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) params;                                                                                         \
+		if (dim == 0)                                                                                          \
+			return layout(0, 1); /* StackReq::EMPTY (mod.rs:968-970) */                                    \
+		/* the reference asks for H, Z and the largest of {householder + reduction, the sweep's workspace, X} */ \
+		const bool vec = compute_left == FaerComputeEigenvectors_Yes || compute_right == FaerComputeEigenvectors_Yes; \
+		return layout(evd_arena_bytes((idx_t) dim, vec, (idx_t) qr_block_size(dim - 1, dim - 1) + 1, (int) sizeof(T)) + 3 * dim * dim * sizeof(T), 64); \
+	}                                                                                                              \
+	FaerEvdStatus libfaer_v0_23_evd_##suf(FaerMatRef A, FaerMatMut UL, FaerMatMut UR, FaerVecMut S, FaerVecMut S_im, \
+					      FaerPar par, FaerMemAlloc mem, FaerEvdParams params)                      \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) mem;                                                                                            \
+		return evd_api<T>(A, UL, UR, S, S_im, params);                                                         \
 	}
 FH_FOR_DTYPES(X)
 #undef X

@@ -512,6 +512,19 @@ template <typename T>
 int svd_dev(MatV<const T> A, MatV<T> U, MatV<T> V, T *S, idx_t ss, idx_t leaf, double qr_ratio_threshold, idx_t qr_blocking_threshold,
 	    idx_t bs_mn, idx_t bs_nn);
 
+// evd/mod.rs:1007 evd_imp, real matrices (schur.hip): wr / wi (n contiguous device entries) <- real and imaginary parts of the
+// eigenvalues of A (n x n, never written), UL / UR (n x n, device) <- left / right eigenvectors in the reference's packed layout
+// unless their .p == nullptr.  All device memory comes from slices of `arena` (arena.h; evd_arena_bytes sizes it);
+// a_is_arena_dense: A is a dense column-major slice the call may overwrite (a staged host operand).  bs: block size of the
+// Hessenberg reduction's Householder factors; shift_count: FaerSchurParams::recommended_shift_count.  Returns 0, or 1 for
+// NoConvergence (a non-finite entry of A, or the iteration cap).
+struct Arena;
+idx_t schur_window_edge(int elem_bytes);
+size_t evd_arena_bytes(idx_t n, bool vectors, idx_t bs, int elem_bytes);
+void evd_last_counts(long out[4]); // {sweeps, window steps, leaf launches, state read-backs} of the calling thread's last evd
+template <typename T>
+int evd_dev(Arena &arena, MatV<const T> A, bool a_is_arena_dense, MatV<T> UL, MatV<T> UR, T *wr, T *wi, idx_t bs, size_t (*shift_count)(size_t, size_t));
+
 // small utility kernels (util.hip)
 template <typename T> void fill_dev(MatV<T> A, DstKind kind, T value);
 template <typename T> void copy_dev(MatV<T> dst, MatV<const T> src);

@@ -131,6 +131,16 @@ typedef struct FaerEvdStatus {
 		struct { size_t padding; } no_convergence;
 	};
 } FaerEvdStatus;
+/* general EVD: faer.h:106-126, lib.rs:2402-2457 (evd/hessenberg.rs:8-25, evd/schur/mod.rs:5-36, evd/mod.rs:38-81) */
+typedef struct FaerEvdFromSchurParams { size_t recursion_threshold; } FaerEvdFromSchurParams;
+typedef struct FaerHessenbergParams { size_t par_threshold; size_t blocking_threshold; } FaerHessenbergParams;
+typedef struct FaerSchurParams {
+	size_t (*recommended_shift_count)(size_t matrix_dimension, size_t active_block_dimension);
+	size_t (*recommended_deflation_window)(size_t matrix_dimension, size_t active_block_dimension);
+	size_t blocking_threshold;
+	size_t nibble_threshold;
+} FaerSchurParams;
+typedef struct FaerEvdParams { FaerHessenbergParams hessenberg; FaerSchurParams schur; FaerEvdFromSchurParams evd_from_schur; } FaerEvdParams;
 /* SVD: faer.h:87-99, :196-201, :471-490, lib.rs:2327-2366 (svd/mod.rs:22-56, svd/bidiag.rs) */
 typedef enum FaerComputeSvdVectors { FaerComputeSvdVectors_No = 0, FaerComputeSvdVectors_Thin = 1, FaerComputeSvdVectors_Full = 2 } FaerComputeSvdVectors;
 typedef struct FaerBidiagParams { size_t par_threshold; } FaerBidiagParams;
@@ -647,8 +657,51 @@ FAER_HIP_API void libfaer_v0_23_piv_llt_reconstruct_u64_f32(FaerMatMut A, FaerMa
 FAER_HIP_API FaerLayout libfaer_v0_23_piv_llt_inverse_scratch_u64_f32(size_t dim, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_piv_llt_inverse_u64_f32(FaerMatMut A_inv, FaerMatRef L, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerPar par, FaerMemAlloc mem);
 
-#endif /* FAER_HIP_NO_FFI_PROTOTYPES */
 
+/* ---------------------------------------------------------------------------------------------
+ * 2i. General (nonsymmetric) real eigendecomposition (faer-ffi/src/lib.rs:2402-2457; evd/mod.rs:960-1246, evd_real).
+ *     A (n x n) is never written.  S / S_im (n entries each) receive the real / imaginary parts of the eigenvalues.
+ *     UL.ncols == 0 / UR.ncols == 0: left / right eigenvectors not wanted; otherwise n x n.  A real eigenvalue
+ *     (S_im[i] == 0) has its eigenvector in column i.  A complex pair sits at (i, i + 1) with S_im[i] == -S_im[i + 1] != 0,
+ *     S_im[i] > 0: column i holds the real and column i + 1 the imaginary part of the eigenvector of S[i] + i S_im[i]; for UL
+ *     the relation is ul^H A = s ul^H (evd/mod.rs:1325-1352).  Vectors are not normalised (as in the reference).
+ *     Hessenberg reduction (csrc/condense.hip), real Schur form by multishift QR sweeps with LDS-resident windows and
+ *     double-shift leaves, back substitution on the quasi-triangular factor, two triangular products (csrc/schur.hip).
+ *     Honoured: params.schur.recommended_shift_count (called on the host once per sweep with (n, active block size); the
+ *     result is rounded down to an even number and clamped to 2 .. min(active - 1, 2 * (W / 6)), W = 96 for f64 and 128 for
+ *     f32, what a bulge chain in one window holds).  Accepted and unused: par, mem, params.hessenberg,
+ *     params.schur.recommended_deflation_window and nibble_threshold (no aggressive early deflation: the classical
+ *     small-subdiagonal test only), params.schur.blocking_threshold (an active block of at most W rows is finished by the
+ *     leaf kernel) and params.evd_from_schur.recursion_threshold (every eigenvector is one column-oriented solve).
+ *     NoConvergence: a non-finite entry of A (checked on the device before anything else), or the iteration cap
+ *     30 max(10, n) of sweeps / of a leaf.  Range: the eigenvalues are right for entries anywhere in the floating-point range
+ *     (the Schur stage forms no squares of entries).  The eigenvectors are not: the closed-form solves of the 2 x 2 diagonal
+ *     blocks square entries of the Schur form (a * a - b * c), as the reference's do (evd/mod.rs:670-881), so with entries
+ *     beyond the square root of the largest or smallest number a call that asks for vectors may return Ok with vectors that
+ *     hold Inf, NaN or zeros.  Scale such a matrix by a power of two first; the eigenvalues scale with it, the vectors do not
+ *     change.  Violated shape preconditions abort.  Host or device operands, any strides, on the
+ *     caller's stream; the call returns after its last kernel has finished.  The scratch query needs no device.
+ *     faer_hip_default_recommended_shift_count / _deflation_window are the reference's defaults (evd/schur/mod.rs:59-107),
+ *     the two function pointers of libfaer_v0_23_SchurParams_*.
+ * --------------------------------------------------------------------------------------------- */
+FAER_HIP_API size_t faer_hip_default_recommended_shift_count(size_t matrix_dimension, size_t active_block_dimension);
+FAER_HIP_API size_t faer_hip_default_recommended_deflation_window(size_t matrix_dimension, size_t active_block_dimension);
+FAER_HIP_API FaerHessenbergParams libfaer_v0_23_HessenbergParams_f64(void);
+FAER_HIP_API FaerHessenbergParams libfaer_v0_23_HessenbergParams_f32(void);
+FAER_HIP_API FaerSchurParams libfaer_v0_23_SchurParams_f64(void);
+FAER_HIP_API FaerSchurParams libfaer_v0_23_SchurParams_f32(void);
+FAER_HIP_API FaerEvdFromSchurParams libfaer_v0_23_EvdFromSchurParams_f64(void);
+FAER_HIP_API FaerEvdFromSchurParams libfaer_v0_23_EvdFromSchurParams_f32(void);
+FAER_HIP_API FaerEvdParams libfaer_v0_23_EvdParams_f64(void);
+FAER_HIP_API FaerEvdParams libfaer_v0_23_EvdParams_f32(void);
+FAER_HIP_API FaerLayout libfaer_v0_23_evd_scratch_f64(size_t dim, FaerComputeEigenvectors compute_left, FaerComputeEigenvectors compute_right, FaerPar par, FaerEvdParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_evd_scratch_f32(size_t dim, FaerComputeEigenvectors compute_left, FaerComputeEigenvectors compute_right, FaerPar par, FaerEvdParams params);
+FAER_HIP_API FaerEvdStatus libfaer_v0_23_evd_f64(FaerMatRef A, FaerMatMut UL, FaerMatMut UR, FaerVecMut S, FaerVecMut S_im, FaerPar par, FaerMemAlloc mem, FaerEvdParams params);
+FAER_HIP_API FaerEvdStatus libfaer_v0_23_evd_f32(FaerMatRef A, FaerMatMut UL, FaerMatMut UR, FaerVecMut S, FaerVecMut S_im, FaerPar par, FaerMemAlloc mem, FaerEvdParams params);
+#endif /* FAER_HIP_NO_FFI_PROTOTYPES */
+/* debug / measurement: {sweeps, window steps, leaf launches, state read-backs} of the calling thread's last evd; the window edge W */
+FAER_HIP_API void faer_hip_debug_evd_last_counts(long out[4]);
+FAER_HIP_API size_t faer_hip_evd_window_edge(FaerHipDType dtype);
 /* ---------------------------------------------------------------------------------------------
  * 3. Runtime control (new: the reference has no device).
  * --------------------------------------------------------------------------------------------- */
