@@ -3,19 +3,39 @@ path (one leaf for n <= W, window sweeps above, W the window edge of the dtype),
 project's standing families (host operands, padded / offset / transposed views, a non-blocking caller stream, the ends of the
 floating-point range, a poisoned scratch pool).
 
-Bound.  For every input numpy's eig (LAPACK geev in the same dtype) is run on the CPU on the same matrix and its residual
-r_np = |A V - V L|_F / (|A|_F |V|_F) measured; the bound of the case is 4 max(r_np, n eps).  The factor 4 allows for a
+Bound.  For every input numpy's eig (LAPACK geev in the same dtype) is run on the CPU on the same matrix and two residuals of it
+are measured: the Frobenius quotient r_np = |A V - V L|_F / (|A|_F |V|_F) and the worst column c_np = max_i |A v_i - l_i v_i|_2 /
+(|A|_F |v_i|_2) (tests/evd_cases.py column_residuals, in fp64, every column scaled by its own largest entry).  The code is held to
+4 max(r_np, n eps) and, per column and per vector set, to 4 max(c_np, n eps): the back substitution does not normalise, its columns
+differ in norm by up to 1 / sqrt(min positive), and the quotient of Frobenius norms sees only the largest.  The factor 4 allows for a
 different shift sequence and the missing early deflation, both backward stable at the same order.  Measured r_np (in units of
-eps of the dtype) on the inputs of this file: float64, N(0,1): 0.5 (n = 2), 2.3 (3), 2.1 (95), 2.2 (96), 2.0 (97), 2.1 (195), 1.8
-(337); symmetric 1.4 .. 1.8, triangular 0 .. 0.2, block diagonal 0 .. 1.8, cyclic 1.4 .. 2.9, normal 0.1 .. 1.8.  float32: at most
-0.2 for every kind and size (numpy's eig of a float32 matrix rounds a double-precision result).  All are below n eps from n = 3
-on, so the bound in force is 4 n eps (n = 2: 8 eps, n = 1: 4 eps; the code's residuals there were 0.6 and 0)."""
+eps of the dtype) on the six normal or random kinds: float64, N(0,1): 0.5 (n = 2), 2.3 (3), 2.1 (95), 2.2 (96), 2.0 (97), 2.1 (195), 1.8
+(337); symmetric 1.4 .. 1.8, triangular 0 .. 0.2, block diagonal 0 .. 1.8, cyclic 1.4 .. 2.9, normal 0.1 .. 1.8; c_np is at most 5.8
+(normal, n = 96).  float32: at most 0.4 for every kind and size (numpy's eig of a float32 matrix rounds a double-precision result).
+All are below n eps from n = 3 on, so the bounds in force are 4 n eps (n = 2: 8 eps, n = 1: 4 eps; the code's residuals there were 0.6
+and 0).
+
+The non-normal kinds (test_evd_non_normal_kinds), c_np / the code's worst column of either vector set / bound, in eps:
+float64: graded_triangular and graded_quasi (n = 96) 0.00 / 0.00 / 384; jordan 0.16 / 7.3 / 120 (n = 30), 0.09 / 13.2 / 388 (97);
+repeated_blocks 0.07 / 35.3 / 120 (30), 0.03 / 59.4 / 388 (97); rotated_* 0.97 .. 2.99 / 0.96 .. 3.13 / 4 n; scaled_similarity 0.00 /
+0.21 .. 0.71 / 4 n.  float32 (c_np at most 0.04): graded_triangular 27.2 / 384, graded_quasi 14.8 / 384; jordan 7.3 / 120 (30), 15.2 /
+516 (129); repeated_blocks 35.0 / 120 (30), 97.5 / 516 (129); rotated_* 0.39 .. 6.27 / 4 n; scaled_similarity 28.4 / 508 (127), 43.0
+/ 516 (129), 52.2 / 1036 (259).  The largest component of the graded outputs is 1.2e152 (triangular) and 5.5e153 (quasi) under the
+fp64 threshold 6.7e153, 3.9e18 under the fp32 threshold 9.2e18; unscaled, the vectors pass 1e290 (tests/test_evd_cases.py).
+
+Spectrum.  Where the input is not defective the computed eigenvalues are assigned one to one to those of numpy's eig in fp64 of the
+dtype-rounded input, each within radius_i = c n eps kappa_i |A|_F of its reference value (tests/evd_cases.py assign_spectrum,
+reference_spectrum): kappa_i = |x_i| |y_i| / |y_i^H x_i| with the left vectors from inv(X), c = 4 for fp32 and 8 for fp64 inputs,
+where the reference's own error is of the same order.  numpy's eig in the dtype of the input passes this on every such input
+(tests/test_evd_cases.py).  A residual alone passes when an eigenpair is reported twice and another is missing."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import evd_cases as ec
 import range_cases as RC
+from evd_cases import KINDS, make, unpack
 from gpu_util import EPS, guard_intact, init_gpu, ordered_call, place, same_result, to_dev, to_host, view_box
 
 pytestmark = pytest.mark.gpu
@@ -29,64 +49,25 @@ def sizes(dtype):
     return [1, 2, 3, W - 1, W, W + 1, 2 * W + 3, {96: 337, 128: 449}[W]]
 
 
-def make(kind, n, dtype, seed=0):
-    """(matrix, known eigenvalues or None)"""
-    rng = np.random.default_rng(1000 * n + seed)
-    if kind == "normal01":
-        return np.asarray(rng.standard_normal((n, n)), dtype=dtype), None
-    if kind == "symmetric":
-        x = rng.standard_normal((n, n))
-        return np.asarray(x + x.T, dtype=dtype), None
-    if kind == "triangular":
-        return np.asarray(np.triu(rng.standard_normal((n, n))), dtype=dtype), None
-    if kind == "block_diagonal":
-        a = np.zeros((n, n))
-        cuts = sorted({0, min(n, max(1, n // 7)), min(n, max(2, n // 7 + (2 * n) // 3)), n})  # unequal blocks, the first one small
-        for lo, hi in zip(cuts[:-1], cuts[1:]):
-            a[lo:hi, lo:hi] = rng.standard_normal((hi - lo, hi - lo))
-        return np.asarray(a, dtype=dtype), None
-    if kind == "cyclic":
-        a = np.zeros((n, n))
-        a[np.arange(1, n), np.arange(n - 1)] = 1.0
-        a[0, n - 1] = 1.0
-        return np.asarray(a, dtype=dtype), np.exp(2j * np.pi * np.arange(n) / n)
-    if kind == "normal":
-        b = np.zeros((n, n))
-        lam = []
-        i = 0
-        while i < n:
-            if i + 1 < n and rng.random() < 0.6:
-                x, y = rng.standard_normal(2)
-                b[i:i + 2, i:i + 2] = [[x, y], [-y, x]]
-                lam += [x + 1j * y, x - 1j * y]
-                i += 2
-            else:
-                b[i, i] = rng.standard_normal()
-                lam.append(b[i, i] + 0j)
-                i += 1
-        q, _ = np.linalg.qr(rng.standard_normal((n, n)))
-        return np.asarray(q @ b @ q.T, dtype=dtype), np.array(lam)
-    raise ValueError(kind)
-
-
-KINDS = ["normal01", "symmetric", "triangular", "block_diagonal", "cyclic", "normal"]
-_BOUNDS = {}
+_PRINTED = set()
 
 
 def bound(a, key):
-    """4 max(residual of numpy's eig in the dtype of a, n eps), computed once per input"""
-    if key not in _BOUNDS:
-        n = a.shape[0]
-        w, v = np.linalg.eig(a)
-        a64 = a.astype(np.float64)
-        r = np.linalg.norm(a64 @ v - v * w) / max(np.linalg.norm(a64) * np.linalg.norm(v), 1e-300)
+    """4 max(Frobenius quotient of numpy's eig in the dtype of a, n eps), computed once per input"""
+    return _bounds(a, key)[0]
+
+
+def _bounds(a, key):
+    bf, bc = ec.bounds(a, key)
+    if key not in _PRINTED:
+        _PRINTED.add(key)
+        _, rf, rc = ec.numpy_same_dtype(a, key)
         e = float(EPS[a.dtype])
-        print(f"numpy eig residual {key}: {r / e:.2f} eps (n eps = {n} eps)")
-        _BOUNDS[key] = 4 * max(r, n * e)
-    return _BOUNDS[key]
+        print(f"numpy eig {key}: Frobenius quotient {rf / e:.2f} eps, worst column {rc / e:.2f} eps (n eps = {a.shape[0]} eps)")
+    return bf, bc
 
 
-def run(F, a, left=True, right=True, order="F"):
+def run(F, a, left=True, right=True, order="F", params=None):
     import torch
 
     n = a.shape[0]
@@ -96,35 +77,16 @@ def run(F, a, left=True, right=True, order="F"):
     si = torch.full((n,), -7.5, dtype=tdt, device="cuda")
     ul = torch.full((n, n), -7.5, dtype=tdt, device="cuda").t() if left else None
     ur = torch.full((n, n), -7.5, dtype=tdt, device="cuda").t() if right else None
-    tag = F.evd(da, s, si, ul, ur)
+    tag = F.evd(da, s, si, ul, ur, params=params)
     F.synchronize()
     assert np.array_equal(to_host(da), a, equal_nan=True), "A was written"
     return tag, s.cpu().numpy(), si.cpu().numpy(), (ul.cpu().numpy() if left else None), (ur.cpu().numpy() if right else None)
 
 
-def unpack(s, si, u):
-    """complex eigenvalues and eigenvector columns from the packed layout; asserts the pair layout of S_im"""
-    n = s.shape[0]
-    lam = s.astype(np.float64) + 1j * si.astype(np.float64)
-    V = None if u is None else np.zeros((n, n), complex)
-    i = 0
-    while i < n:
-        if si[i] == 0:
-            if u is not None:
-                V[:, i] = u[:, i]
-            i += 1
-        else:
-            assert i + 1 < n and si[i] == -si[i + 1] and si[i] > 0 and s[i] == s[i + 1], f"S_im does not hold a pair at {i}"
-            if u is not None:
-                V[:, i] = u[:, i].astype(np.float64) + 1j * u[:, i + 1].astype(np.float64)
-                V[:, i + 1] = V[:, i].conj()
-            i += 2
-    return lam, V
-
-
-def check_vectors(a, s, si, ul, ur, b, what):
-    a64 = a.astype(np.float64)
-    na = max(np.linalg.norm(a64), 1e-300)
+def check_vectors(a, s, si, ul, ur, key, what):
+    """both verdicts on every vector set given: the Frobenius quotient and the worst column, each against its bound of the case `key`"""
+    bf, bc = _bounds(a, key)
+    e = float(EPS[a.dtype])
     lam = None
     for side, u in (("right", ur), ("left", ul)):
         if u is None:
@@ -132,12 +94,14 @@ def check_vectors(a, s, si, ul, ur, b, what):
         assert np.isfinite(u).all(), (what, side)
         lam, V = unpack(s, si, u)
         assert (np.abs(V).max(axis=0) > 0).all(), (what, side, "a zero eigenvector column")
-        if side == "right":
-            r = np.linalg.norm(a64 @ V - V * lam) / (na * np.linalg.norm(V))
-        else:
-            r = np.linalg.norm(V.conj().T @ a64 - lam[:, None] * V.conj().T) / (na * np.linalg.norm(V))
-        print(f"{what} {side} residual {r / float(EPS[a.dtype]):.2f} eps, bound {b / float(EPS[a.dtype]):.0f} eps")
-        assert r <= b, (what, side, r, b)
+        cols = ec.column_residuals(a, lam, V, side)
+        # (the Frobenius quotient squares the entries: columns scaled down together, by a power of two, keep it finite)
+        r = ec.frobenius_quotient(a, lam, np.ldexp(V.real, -600) + 1j * np.ldexp(V.imag, -600), side) if np.abs(V).max() > 1e150 \
+            else ec.frobenius_quotient(a, lam, V, side)
+        print(f"{what} {side}: Frobenius quotient {r / e:.2f} eps (bound {bf / e:.0f} eps), worst column {cols.max() / e:.2f} eps at {cols.argmax()} "
+              f"(bound {bc / e:.0f} eps)")
+        assert r <= bf, (what, side, r, bf)
+        assert cols.max() <= bc, (what, side, int(cols.argmax()), cols.max() / e, bc / e)
     if lam is None:
         lam, _ = unpack(s, si, None)
     return lam
@@ -156,11 +120,14 @@ def test_evd_kinds_and_sizes(kind, dtype):
     for n in sizes(dtype):
         a, known = make(kind, n, dtype)
         what = f"{kind} n={n} {np.dtype(dtype).name}"
-        b = bound(a, (kind, n, np.dtype(dtype).name))
+        key = (kind, n, np.dtype(dtype).name)
+        b = bound(a, key)
         tag, s, si, ul, ur = run(F, a)
         assert tag == F.EVD_OK, what
         print(what, F.debug_evd_last_counts())
-        lam = check_vectors(a, s, si, ul, ur, b, what)
+        lam = check_vectors(a, s, si, ul, ur, key, what)
+        ref, radius = ec.reference_spectrum(a, key)
+        assert ec.assign_spectrum(lam, ref, radius), (what, "the spectrum is not that of the fp64 reference")
         na = np.linalg.norm(a.astype(np.float64))
         if kind == "symmetric":
             assert (si == 0).all(), what
@@ -181,8 +148,8 @@ def test_evd_kinds_and_sizes(kind, dtype):
             tagl, sl, sil, ull, _ = run(F, a, left=True, right=False)
             tagr, sr, sir, _, urr = run(F, a, left=False, right=True)
             assert tagl == F.EVD_OK and tagr == F.EVD_OK
-            check_vectors(a, sl, sil, ull, None, b, what + " UL only")
-            check_vectors(a, sr, sir, None, urr, b, what + " UR only")
+            check_vectors(a, sl, sil, ull, None, key, what + " UL only")
+            check_vectors(a, sr, sir, None, urr, key, what + " UR only")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -198,7 +165,7 @@ def test_non_finite_input_is_no_convergence(bad, dtype):
     a, _ = make("normal01", 40, dtype)
     tag, s, si, ul, ur = run(F, a)
     assert tag == F.EVD_OK
-    check_vectors(a, s, si, ul, ur, bound(a, ("normal01", 40, np.dtype(dtype).name)), "after a failure")
+    check_vectors(a, s, si, ul, ur, ("normal01", 40, np.dtype(dtype).name), "after a failure")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -223,7 +190,6 @@ def test_host_operands(dtype):
     F = init_gpu()
     for n in family_sizes(dtype):
         a, _ = make("normal01", n, dtype)
-        b = bound(a, ("normal01", n, np.dtype(dtype).name))
         _, sd, sid, uld, urd = run(F, a)
         # a faer::Mat (column major), a row-major matrix and a strided view with strided S: the same values as device operands
         for layout in ("F", "C", "strided"):
@@ -245,7 +211,7 @@ def test_host_operands(dtype):
             if layout == "strided":
                 assert (parent[0::2] == -7.5).all() and (parent[:, :2] == -7.5).all() and (parent[:, n + 2:] == -7.5).all()
             assert np.array_equal(s, sd) and np.array_equal(si, sid) and np.array_equal(ul, uld) and np.array_equal(ur, urd), (n, layout)
-            check_vectors(a, s, si, ul, ur, b, f"host {layout} n={n}")
+            check_vectors(a, s, si, ul, ur, ("normal01", n, np.dtype(dtype).name), f"host {layout} n={n}")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -335,7 +301,6 @@ def test_poisoned_scratch_pool(dtype):
     try:
         for n in family_sizes(dtype):
             a, _ = make("normal01", n, dtype)
-            b = bound(a, ("normal01", n, np.dtype(dtype).name))
             for host in (False, True):
                 def call():
                     if not host:
@@ -359,6 +324,93 @@ def test_poisoned_scratch_pool(dtype):
                     assert x[0] == y[0] == F.EVD_OK
                     for i in range(1, 5):
                         assert np.array_equal(x[i], y[i]), (n, host, what, ("s", "s_im", "ul", "ur")[i - 1])
-                check_vectors(a, ff[1], ff[2], ff[3], ff[4], b, f"poisoned n={n} host={host}")
+                check_vectors(a, ff[1], ff[2], ff[3], ff[4], ("normal01", n, np.dtype(dtype).name), f"poisoned n={n} host={host}")
     finally:
         F.debug_scratch_fill(-1)
+
+
+def non_normal_sizes(kind, dtype):
+    W = WEDGE[np.dtype(dtype)]
+    if kind in ("graded_triangular", "graded_quasi"):
+        return [ec.GUARD_N[np.dtype(dtype)]]
+    if kind in ("jordan", "repeated_blocks"):
+        return [30, W + 1]
+    return [W - 1, W + 1, 2 * W + 3]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("kind", ec.NEW_KINDS)
+def test_evd_non_normal_kinds(kind, dtype):
+    """the kinds of tests/evd_cases.py that reach the overflow guard and the divisor floor of the back substitution, and dense
+    inputs with the same Schur forms: both vector sets under both verdicts, the spectrum of the non-defective ones assigned"""
+    F = init_gpu()
+    e = float(EPS[np.dtype(dtype)])
+    for n in non_normal_sizes(kind, dtype):
+        a, known, defective = ec.generate(kind, n, dtype)
+        key = (kind, n, np.dtype(dtype).name)
+        what = f"{kind} n={n} {np.dtype(dtype).name}"
+        tag, s, si, ul, ur = run(F, a)
+        assert tag == F.EVD_OK, what
+        assert np.isfinite(s).all() and np.isfinite(si).all(), what
+        print(what, F.debug_evd_last_counts())
+        lam = check_vectors(a, s, si, ul, ur, key, what)  # (finite, no zero column, the pair layout of S_im, both verdicts)
+        if not defective:
+            ref, radius = ec.reference_spectrum(a, key)
+            assert ec.assign_spectrum(lam, ref, radius), (what, "the spectrum is not that of the fp64 reference")
+        if kind in ec.TRIANGULAR_KINDS:
+            # a Schur form already: the real parts are the diagonal, an imaginary part is a product of two square roots
+            assert np.array_equal(np.sort(s), np.sort(np.diag(a))), what
+            assert ec.assign_spectrum(lam, known, 4 * e * np.abs(known).max()), what
+        if kind in ("graded_triangular", "graded_quasi"):
+            # the guard fired (tests/test_evd_cases.py: the unscaled vectors pass its threshold) and left no component beyond it
+            big = ec.guard_threshold(dtype)
+            for side, u in (("right", ur), ("left", ul)):
+                print(f"{what} {side}: largest component {np.abs(u).max():.3e}, threshold {big:.3e}")
+                assert np.abs(u).max() <= big * np.sqrt(n), (what, side)  # (U = Z X with Z orthogonal, here the identity)
+            # each vector set alone: the left solve runs on the reversed transposed view, its guard sees other strides
+            tagl, sl, sil, ull, _ = run(F, a, left=True, right=False)
+            tagr, sr, sir, _, urr = run(F, a, left=False, right=True)
+            assert tagl == F.EVD_OK and tagr == F.EVD_OK
+            check_vectors(a, sl, sil, ull, None, key, what + " UL only")
+            check_vectors(a, sr, sir, None, urr, key, what + " UR only")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("ret", [0, 3, 64, 2 ** 63 + 5])
+def test_shift_count_callback(ret, dtype):
+    """a caller's recommended_shift_count that returns zero, an odd count, more than the window carries and a value that is
+    negative as a long: the driver clamps each to an even count in [2, 2 max_bulges(W)] and the decomposition is as good"""
+    F = init_gpu()
+    W = WEDGE[np.dtype(dtype)]
+    n = 2 * W + 3
+    a, _ = make("normal01", n, dtype)
+    key = ("normal01", n, np.dtype(dtype).name)
+    calls = []
+
+    def shift_count(dim, active):
+        calls.append((dim, active))
+        return ret
+
+    cb = F.SHIFT_FN(shift_count)  # (alive until the call has returned)
+    suf = "f64" if dtype == np.float64 else "f32"
+    pf = getattr(F.lib(), f"libfaer_v0_23_EvdParams_{suf}")
+    pf.restype = F.EvdParams
+    params = pf()
+    params.schur.recommended_shift_count = cb
+    tag, s, si, ul, ur = run(F, a, params=params)
+    assert tag == F.EVD_OK
+    counts = F.debug_evd_last_counts()
+    print(f"shift count {ret} n={n} {np.dtype(dtype).name}: {counts}, {len(calls)} calls, first {calls[:1]}")
+    lam = check_vectors(a, s, si, ul, ur, key, f"shift count {ret} n={n}")
+    ref, radius = ec.reference_spectrum(a, key)
+    assert ec.assign_spectrum(lam, ref, radius)
+    assert calls and all(d == n and W < m <= n for d, m in calls), calls[:4]
+    assert counts["sweeps"] > 0 and len(calls) == counts["sweeps"]
+    if ret == 64 and dtype == np.float32:
+        # clamped to 2 max_bulges(W) = 42 shifts: the chain of 21 bulges fills the window exactly, s + 4 + 3 (nb - 1) = W, and the
+        # first sweep, on an active block of m rows ((ihi - 2) - (ilo - 1) = m - 1), takes SweepPlan's number of window steps
+        nb = 21
+        assert (W - 3 * nb - 1) + 4 + 3 * (nb - 1) == W
+        first = -(-((calls[0][1] - 1) + 3 * (nb - 1)) // (W - 3 * nb - 1))
+        assert counts["window_steps"] >= first, (counts, first)
+    del cb

@@ -3,13 +3,18 @@ barrier) and runs the whole sweep loop -- prepare, shifts, window steps, leaves,
 edge, so that matrices of a few dozen rows take every path.  No GPU.
 
 Checked against numpy in fp64: the decomposition H = Z T Z^T, the form of T, the eigenvalues and the eigenvector residual.
-Bound: 4 max(numpy's own residual, n eps), as in test_gpu_evd_general.py."""
+Bound: 4 max(numpy's own residual, n eps), as in test_gpu_evd_general.py.
+
+The non-normal kinds of tests/evd_cases.py run here first, under the per-column verdict and the assignment of the spectrum: the
+overflow guard and the divisor floor of eigvec_block are reached by them alone, and a defect there shows without a GPU."""
 import os
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+import evd_cases as ec
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "host", "schur_host.cpp")
@@ -120,3 +125,69 @@ def test_iteration_cap_is_reported(exe, tmp_path):
     h[3, 3] = np.nan
     status = run(exe, tmp_path, h, "f64")[0]
     assert status == 1
+
+
+def hessenberg_form(a):
+    """Q^T a Q upper Hessenberg, by Householder reflectors in fp64"""
+    h = np.array(a, dtype=np.float64)
+    n = h.shape[0]
+    for k in range(n - 2):
+        x = h[k + 1:, k].copy()
+        if not x[1:].any():
+            continue
+        x[0] += np.copysign(np.linalg.norm(x), x[0])
+        x /= np.linalg.norm(x)
+        h[k + 1:, :] -= 2 * np.outer(x, x @ h[k + 1:, :])
+        h[:, k + 1:] -= 2 * np.outer(h[:, k + 1:] @ x, x)
+        h[k + 2:, k] = 0
+    return h
+
+
+NON_NORMAL = [(k, n) for k in ec.NEW_KINDS for n in (W, 2 * W + 3)] + [(k, "guard") for k in ("graded_triangular", "graded_quasi")]
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("kind,n", NON_NORMAL)
+def test_non_normal_kinds_on_the_host(exe, tmp_path, kind, n, dtype):
+    np_t = np.float64 if dtype == "f64" else np.float32
+    eps = ec.eps_of(np_t)
+    n = ec.GUARD_N[np.dtype(np_t)] if n == "guard" else n
+    a, known, defective = ec.generate(kind, n, np_t)
+    unrotated = kind in ec.TRIANGULAR_KINDS
+    h = a if unrotated else hessenberg_form(a).astype(np_t)  # (the triangular kinds are Hessenberg matrices already)
+    assert np.array_equal(np.tril(h, -2), np.zeros_like(h))
+    status, counts, wr, wi, t, z, x = run(exe, tmp_path, h.astype(np.float64), dtype)
+    assert status == 0
+    assert np.isfinite(x).all() and np.isfinite(z).all()
+    lam = wr + 1j * wi
+    v = complex_vectors(wi, z @ x)
+    assert (np.abs(v).max(axis=0) > 0).all()
+    key = ("host", kind, n, dtype)
+    _, bc = ec.bounds(h, key)
+    np_col = ec.numpy_same_dtype(h, key)[2]
+    r = ec.column_residuals(h, lam, v)
+    norms = np.linalg.norm(v / np.abs(v).max(), axis=0) * np.abs(v).max()
+    print(f"{kind} n={n} {dtype}: sweeps/steps/leaves {counts}, numpy's worst column {np_col / eps:.2f} eps, worst column {r.max() / eps:.2f} eps, "
+          f"bound {bc / eps:.0f} eps, column norms {norms.min():.3g} .. {norms.max():.3g}")
+    assert r.max() <= bc, (r.argmax(), r.max() / eps, bc / eps)
+    if not defective:
+        ref, radius = ec.reference_spectrum(h, key)
+        assert ec.assign_spectrum(lam, ref, radius)
+    if unrotated:
+        # nothing to do for the sweeps: T is the input, the real eigenvalues are its diagonal entries exactly and an imaginary part
+        # is a product of two square roots (three roundings)
+        assert np.array_equal(t, h.astype(np.float64))
+        assert np.array_equal(wr, np.diag(h).astype(np.float64))
+        assert ec.assign_spectrum(lam, known, 4 * eps * np.abs(known).max())
+    if kind in ("graded_triangular", "graded_quasi"):
+        # the guard fired: in extended precision the unscaled vectors pass its threshold, here no component does, and the
+        # largest one is what the same substitution with the same rescalings leaves
+        big = ec.guard_threshold(np_t)
+        top, sites, out = ec.guard_sites(h, np_t)
+        print(f"  largest unscaled component {float(top):.3e}, guard at {sorted(sites)}, largest component {np.abs(x).max():.3e}, "
+              f"in extended precision {float(out):.3e}, threshold {big:.3e}")
+        assert top > big or (dtype == "f64" and n == W)  # (24 rows do not reach the fp64 threshold)
+        assert np.abs(x).max() <= big
+        assert np.abs(x).max() == pytest.approx(float(out), rel=1e-3)
+        if n == ec.GUARD_N[np.dtype(np_t)]:
+            assert len(sites) == (4 if kind == "graded_quasi" else 1)
