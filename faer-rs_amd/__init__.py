@@ -180,6 +180,33 @@ class EvdParams(C.Structure):
     _fields_ = [("hessenberg", HessenbergParams), ("schur", SchurParams), ("evd_from_schur", EvdFromSchurParams)]
 
 
+class GeneralizedHessenbergParams(C.Structure):
+    _fields_ = [("block_size", C.c_size_t), ("blocking_threshold", C.c_size_t)]
+
+
+class GeneralizedSchurParams(C.Structure):
+    """include/faer_hip.h FaerGeneralizedSchurParams: three function pointers (matrix dimension, active block dimension) -> size_t, two sizes"""
+    _fields_ = [("relative_cost_estimate_of_shift_chase_to_matmul", SHIFT_FN), ("recommended_shift_count", SHIFT_FN),
+                ("recommended_deflation_window", SHIFT_FN), ("blocking_threshold", C.c_size_t), ("nibble_threshold", C.c_size_t)]
+
+
+class GevdFromSchurParams(C.Structure):
+    _fields_ = [("padding", C.c_size_t)]
+
+
+class GevdParams(C.Structure):
+    """include/faer_hip.h FaerGevdParams {hessenberg, schur, evd_from_schur}"""
+    _fields_ = [("hessenberg", GeneralizedHessenbergParams), ("schur", GeneralizedSchurParams), ("evd_from_schur", GevdFromSchurParams)]
+
+
+class GevdStatus(C.Structure):
+    """include/faer_hip.h FaerGevdStatus: tag (0 Ok, 1 NoConvergence), then a union of one size_t"""
+    _fields_ = [("tag", C.c_int), ("padding", C.c_size_t)]
+
+
+GEVD_OK, GEVD_NO_CONVERGENCE = 0, 1
+
+
 class BidiagParams(C.Structure):
     _fields_ = [("par_threshold", C.c_size_t)]
 
@@ -610,6 +637,39 @@ def debug_evd_last_counts():
 def evd_window_edge(dtype):
     """W: the edge of the LDS-resident window of the Schur kernels (96 for float64, 128 for float32)"""
     f = lib().faer_hip_evd_window_edge
+    f.restype = C.c_size_t
+    return int(f(C.c_int(DTYPE_F64 if np.dtype(dtype) == np.float64 else DTYPE_F32)))
+
+
+def generalized_evd(a, b, alpha, alpha_im, beta, ul=None, ur=None, params=None, par=PAR_SEQ):
+    """faer::linalg::gevd::gevd_real (gevd/mod.rs:130): eigenvalues (alpha + i alpha_im) / beta of the real pair (`a`, `b`) (n x n,
+    never written) into the 1-D `alpha`, `alpha_im`, `beta`; with `ul` / `ur` (n x n) the left / right eigenvectors in the packed
+    layout of evd.  Returns the status tag (GEVD_OK or GEVD_NO_CONVERGENCE)."""
+    suf, _, _ = _dtype_suffix(a)
+    L = lib()
+    if params is None:
+        pf = getattr(L, f"libfaer_v0_23_GevdParams_{suf}")
+        pf.restype = GevdParams
+        params = pf()
+    n = a.shape[0]
+    ulm = _mat(ul, MatMut) if ul is not None else MatMut(None, n, 0, 1, n)
+    urm = _mat(ur, MatMut) if ur is not None else MatMut(None, n, 0, 1, n)
+    fn = getattr(L, f"libfaer_v0_23_generalized_evd_{suf}")
+    fn.restype = GevdStatus
+    st = fn(_mat(a, MatMut), _mat(b, MatMut), ulm, urm, _vec(alpha, VecMut), _vec(alpha_im, VecMut), _vec(beta, VecMut), par, MemAlloc(None, 0), params)
+    return st.tag
+
+
+def debug_gevd_last_counts():
+    """{multishift sweeps, window steps, leaf launches, state read-backs, infinite eigenvalues deflated} of the calling thread's last generalized_evd"""
+    out = (C.c_long * 5)()
+    lib().faer_hip_debug_gevd_last_counts(out)
+    return dict(zip(("sweeps", "window_steps", "leaves", "readbacks", "infinite_deflations"), (int(v) for v in out)))
+
+
+def gevd_window_edge(dtype):
+    """W: the edge of the LDS-resident leaf and window of the QZ kernels (64 for float64, 96 for float32)"""
+    f = lib().faer_hip_gevd_window_edge
     f.restype = C.c_size_t
     return int(f(C.c_int(DTYPE_F64 if np.dtype(dtype) == np.float64 else DTYPE_F32)))
 

@@ -2,6 +2,7 @@
 // citations of every entry point).  This file only validates shapes, stages host operands and forwards
 // to the device drivers; there is deliberately no CPU compute path here.
 #include <atomic>
+#include <limits>
 
 #include "arena.h"
 #include "common.h"
@@ -670,6 +671,65 @@ template <typename T> FaerEvdStatus evd_api(FaerMatRef A, FaerMatMut UL, FaerMat
 		}
 	}
 	st.tag = r == 0 ? FaerEvdStatus_Ok : FaerEvdStatus_NoConvergence;
+	return st;
+}
+
+// gevd/mod.rs:130-320 behind lib.rs:2459-2520 (U.ncols == 0: no eigenvectors).  One arena holds the working matrices of gevd_dev,
+// the three eigenvalue vectors and the staged images of host operands.
+template <typename T>
+FaerGevdStatus gevd_api(FaerMatMut Am, FaerMatMut Bm, FaerMatMut UL, FaerMatMut UR, FaerVecMut Al, FaerVecMut Ai, FaerVecMut Be, FaerGevdParams params)
+{
+	const size_t n = Am.nrows;
+	FH_CHECK(params.schur.recommended_shift_count != nullptr, "generalized_evd: params.schur.recommended_shift_count is NULL");
+	FH_CHECK(Am.ncols == n && Bm.nrows == n && Bm.ncols == n, "generalized_evd: A and B must be square and of one size");
+	FH_CHECK(Al.len == n && Ai.len == n && Be.len == n, "generalized_evd: alpha, alpha_im and beta must have n entries");
+	FH_CHECK(UL.ncols == 0 || (UL.nrows == n && UL.ncols == n), "generalized_evd: UL must be n x n (or have no columns)");
+	FH_CHECK(UR.ncols == 0 || (UR.nrows == n && UR.ncols == n), "generalized_evd: UR must be n x n (or have no columns)");
+	FaerGevdStatus st;
+	memset(&st, 0, sizeof(st));
+	st.tag = FaerGevdStatus_Ok;
+	if (n == 0)
+		return st; // mod.rs:183
+	ctx().ensure_device();
+	const bool want_l = UL.ncols != 0, want_r = UR.ncols != 0;
+	const idx_t N = (idx_t) n, bs0 = (idx_t) qr_block_size(n, n), bs = bs0 < 1 ? 1 : bs0;
+	const FaerMatRef Ar{Am.ptr, Am.nrows, Am.ncols, Am.row_stride, Am.col_stride}, Br{Bm.ptr, Bm.nrows, Bm.ncols, Bm.row_stride, Bm.col_stride};
+	const MatV<const T> a = view<T>(Ar), b = view<T>(Br);
+	const MatV<T> ul = view<T>(UL), ur = view<T>(UR), outs[3] = {vview<T>(Al), vview<T>(Ai), vview<T>(Be)};
+	const bool a_host = !is_device_ptr(a.p), b_host = !is_device_ptr(b.p), ul_host = want_l && !is_device_ptr(ul.p), ur_host = want_r && !is_device_ptr(ur.p);
+	const size_t nn = Arena::padded(n * n * sizeof(T));
+	int r;
+	{
+		Arena ar(gevd_arena_bytes(N, want_l || want_r, bs, (int) sizeof(T)) + 3 * Arena::padded(n * sizeof(T))
+			 + ((size_t) a_host + (size_t) b_host + (size_t) ul_host + (size_t) ur_host) * nn + 512);
+		T *ev[3] = {ar.take<T>(n), ar.take<T>(n), ar.take<T>(n)};
+		const MatV<T> dl = ul_host ? ar.mat<T>(N, N) : (want_l ? ul : MatV<T>{nullptr, N, N, 1, N});
+		const MatV<T> dr = ur_host ? ar.mat<T>(N, N) : (want_r ? ur : MatV<T>{nullptr, N, N, 1, N});
+		const MatV<const T> da = a_host ? ar.copy_in<T>(a).c() : a, db = b_host ? ar.copy_in<T>(b).c() : b;
+		r = gevd_dev<T>(ar, da, db, dl, dr, ev[0], ev[1], ev[2], bs, (idx_t) 48 * 48, params.schur.recommended_shift_count);
+		if (r != 0) { // mod.rs:225-234 (and the same outputs where the iteration cap is reached)
+			const T nan = std::numeric_limits<T>::quiet_NaN();
+			for (int k = 0; k < 3; ++k)
+				fill_dev<T>(MatV<T>{ev[k], N, 1, 1, N}, DST_FULL, nan);
+			if (want_l)
+				fill_dev<T>(dl, DST_FULL, nan);
+			if (want_r)
+				fill_dev<T>(dr, DST_FULL, nan);
+		}
+		for (int k = 0; k < 3; ++k) {
+			const MatV<const T> src{ev[k], N, 1, 1, N};
+			if (is_device_ptr(outs[k].p))
+				copy_dev<T>(outs[k], src);
+			else
+				Arena::copy_out<T>(outs[k], src);
+		}
+		if (ul_host)
+			Arena::copy_out<T>(ul, dl.c());
+		if (ur_host)
+			Arena::copy_out<T>(ur, dr.c());
+		ctx().sync();
+	}
+	st.tag = r == 0 ? FaerGevdStatus_Ok : FaerGevdStatus_NoConvergence;
 	return st;
 }
 
@@ -1601,6 +1661,54 @@ size_t faer_hip_evd_window_edge(FaerHipDType dtype) { return (size_t) schur_wind
 		(void) par;                                                                                            \
 		(void) mem;                                                                                            \
 		return evd_api<T>(A, UL, UR, S, S_im, params);                                                         \
+	}
+FH_FOR_DTYPES(X)
+#undef X
+
+size_t faer_hip_default_relative_cost_estimate_of_shift_chase_to_matmul(size_t n, size_t active)
+{
+	(void) n;
+	(void) active; // gevd/mod.rs:85-91
+	return 10;
+}
+void faer_hip_debug_gevd_last_counts(long out[5]) { gevd_last_counts(out); }
+size_t faer_hip_gevd_window_edge(FaerHipDType dtype) { return (size_t) gevd_window_edge(dtype == FaerHipDType_F64 ? 8 : 4); }
+
+#define X(suf, T)                                                                                                      \
+	FaerGeneralizedHessenbergParams libfaer_v0_23_GeneralizedHessenbergParams_##suf(void)                          \
+	{                                                                                                              \
+		return FaerGeneralizedHessenbergParams{32, 256 * 256}; /* gen_hessenberg/mod.rs */                     \
+	}                                                                                                              \
+	FaerGeneralizedSchurParams libfaer_v0_23_GeneralizedSchurParams_##suf(void)                                    \
+	{                                                                                                              \
+		const FaerSchurParams sp = libfaer_v0_23_SchurParams_##suf(); /* gevd/mod.rs:92-105 */                  \
+		return FaerGeneralizedSchurParams{faer_hip_default_relative_cost_estimate_of_shift_chase_to_matmul, sp.recommended_shift_count, \
+						  sp.recommended_deflation_window, sp.blocking_threshold, sp.nibble_threshold}; \
+	}                                                                                                              \
+	FaerGevdParams libfaer_v0_23_GevdParams_##suf(void)                                                            \
+	{                                                                                                              \
+		return FaerGevdParams{libfaer_v0_23_GeneralizedHessenbergParams_##suf(), libfaer_v0_23_GeneralizedSchurParams_##suf(), \
+				      FaerGevdFromSchurParams{0}};                                                      \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_generalized_evd_scratch_##suf(size_t dim, FaerComputeEigenvectors compute_left,      \
+							       FaerComputeEigenvectors compute_right, FaerPar par, FaerGevdParams params) \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) params;                                                                                         \
+		if (dim == 0)                                                                                          \
+			return layout(0, 1);                                                                           \
+		const bool vec = compute_left == FaerComputeEigenvectors_Yes || compute_right == FaerComputeEigenvectors_Yes; \
+		/* the arena of the call with every operand staged */                                                  \
+		return layout(gevd_arena_bytes((idx_t) dim, vec, (idx_t) qr_block_size(dim, dim) + 1, (int) sizeof(T)) + 4 * dim * dim * sizeof(T) \
+				      + 3 * dim * sizeof(T), 64);                                                       \
+	}                                                                                                              \
+	FaerGevdStatus libfaer_v0_23_generalized_evd_##suf(FaerMatMut A, FaerMatMut B, FaerMatMut UL, FaerMatMut UR, FaerVecMut alpha, \
+							   FaerVecMut alpha_im, FaerVecMut beta, FaerPar par, FaerMemAlloc mem, \
+							   FaerGevdParams params)                                       \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) mem;                                                                                            \
+		return gevd_api<T>(A, B, UL, UR, alpha, alpha_im, beta, params);                                       \
 	}
 FH_FOR_DTYPES(X)
 #undef X

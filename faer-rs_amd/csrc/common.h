@@ -525,6 +525,16 @@ void evd_last_counts(long out[4]); // {sweeps, window steps, leaf launches, stat
 template <typename T>
 int evd_dev(Arena &arena, MatV<const T> A, bool a_is_arena_dense, MatV<T> UL, MatV<T> UR, T *wr, T *wi, idx_t bs, size_t (*shift_count)(size_t, size_t));
 
+// gevd/mod.rs:130 gevd_real (qz.hip): alpha_re / alpha_im / beta (n contiguous device entries each) <- the eigenvalues
+// (alpha_re + i alpha_im) / beta of the pair (A, B) (n x n, never written), UL / UR as in evd_dev.  All device memory comes from
+// slices of `arena` (gevd_arena_bytes sizes it).  bs: block size of the QR of B.  Returns 0, or 1 for NoConvergence.
+idx_t gevd_window_edge(int elem_bytes);
+size_t gevd_arena_bytes(idx_t n, bool vectors, idx_t bs, int elem_bytes);
+void gevd_last_counts(long out[5]); // {sweeps, window steps, QZ launches, state read-backs, infinite deflations} of the last call
+template <typename T>
+int gevd_dev(Arena &arena, MatV<const T> A, MatV<const T> B, MatV<T> UL, MatV<T> UR, T *alpha_re, T *alpha_im, T *beta, idx_t bs, idx_t qr_blocking_threshold,
+	     size_t (*shift_count)(size_t, size_t));
+
 // small utility kernels (util.hip)
 template <typename T> void fill_dev(MatV<T> A, DstKind kind, T value);
 template <typename T> void copy_dev(MatV<T> dst, MatV<const T> src);

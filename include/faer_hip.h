@@ -141,6 +141,25 @@ typedef struct FaerSchurParams {
 	size_t nibble_threshold;
 } FaerSchurParams;
 typedef struct FaerEvdParams { FaerHessenbergParams hessenberg; FaerSchurParams schur; FaerEvdFromSchurParams evd_from_schur; } FaerEvdParams;
+/* generalized EVD: faer.h:132-154, :303-322, lib.rs:2459-2520 (gevd/gen_hessenberg/mod.rs, gevd/mod.rs:37-122) */
+typedef struct FaerGeneralizedHessenbergParams { size_t block_size; size_t blocking_threshold; } FaerGeneralizedHessenbergParams;
+typedef struct FaerGeneralizedSchurParams {
+	size_t (*relative_cost_estimate_of_shift_chase_to_matmul)(size_t matrix_dimension, size_t active_block_dimension);
+	size_t (*recommended_shift_count)(size_t matrix_dimension, size_t active_block_dimension);
+	size_t (*recommended_deflation_window)(size_t matrix_dimension, size_t active_block_dimension);
+	size_t blocking_threshold;
+	size_t nibble_threshold;
+} FaerGeneralizedSchurParams;
+typedef struct FaerGevdFromSchurParams { size_t padding; } FaerGevdFromSchurParams;
+typedef struct FaerGevdParams { FaerGeneralizedHessenbergParams hessenberg; FaerGeneralizedSchurParams schur; FaerGevdFromSchurParams evd_from_schur; } FaerGevdParams;
+typedef enum FaerGevdStatus_Tag { FaerGevdStatus_Ok = 0, FaerGevdStatus_NoConvergence = 1 } FaerGevdStatus_Tag;
+typedef struct FaerGevdStatus {
+	FaerGevdStatus_Tag tag;
+	union {
+		struct { size_t padding; } ok;
+		struct { size_t padding; } no_convergence;
+	};
+} FaerGevdStatus;
 /* SVD: faer.h:87-99, :196-201, :471-490, lib.rs:2327-2366 (svd/mod.rs:22-56, svd/bidiag.rs) */
 typedef enum FaerComputeSvdVectors { FaerComputeSvdVectors_No = 0, FaerComputeSvdVectors_Thin = 1, FaerComputeSvdVectors_Full = 2 } FaerComputeSvdVectors;
 typedef struct FaerBidiagParams { size_t par_threshold; } FaerBidiagParams;
@@ -698,10 +717,41 @@ FAER_HIP_API FaerLayout libfaer_v0_23_evd_scratch_f64(size_t dim, FaerComputeEig
 FAER_HIP_API FaerLayout libfaer_v0_23_evd_scratch_f32(size_t dim, FaerComputeEigenvectors compute_left, FaerComputeEigenvectors compute_right, FaerPar par, FaerEvdParams params);
 FAER_HIP_API FaerEvdStatus libfaer_v0_23_evd_f64(FaerMatRef A, FaerMatMut UL, FaerMatMut UR, FaerVecMut S, FaerVecMut S_im, FaerPar par, FaerMemAlloc mem, FaerEvdParams params);
 FAER_HIP_API FaerEvdStatus libfaer_v0_23_evd_f32(FaerMatRef A, FaerMatMut UL, FaerMatMut UR, FaerVecMut S, FaerVecMut S_im, FaerPar par, FaerMemAlloc mem, FaerEvdParams params);
+/* ---------------------------------------------------------------------------------------------
+ * 2j. Generalized real eigendecomposition (faer-ffi/src/lib.rs:2459-2520; gevd/mod.rs:130-320, gevd_real) of the pair (A, B).
+ *     Eigenvalue i is (alpha[i] + i alpha_im[i]) / beta[i]; beta[i] >= 0, and beta[i] == 0 is an infinite eigenvalue.  UL / UR
+ *     with no columns: not wanted.  Vectors use the packed layout of evd: a real eigenvalue takes column i, a conjugate pair at
+ *     (i, i + 1) takes real part, then imaginary part; ur: beta A x = alpha B x, ul: beta y^H A = alpha y^H B.  Columns are not
+ *     normalised.  A non-finite entry of A or B fills alpha, alpha_im, beta and the wanted vectors with NaN and returns
+ *     NoConvergence.  The reference leaves A and B unspecified after the call; this library works on device copies and does
+ *     not write them.  Operands may be host or device memory with arbitrary element strides; the call runs on the caller's
+ *     stream and takes all its device memory from one arena.
+ *     Path: QR of B, Hessenberg-triangular reduction by rotations in one workgroup, multishift QZ sweeps in LDS windows of edge
+ *     faer_hip_gevd_window_edge with off-window products on the GEMM and an LDS-resident leaf for blocks up to that edge
+ *     (csrc/qz.hip, csrc/qz_core.h), eigenvectors one workgroup per eigenvalue.  schur.recommended_shift_count is called once per
+ *     sweep and clamped to [2, twice the bulges a window carries], even.  Accepted and unused: hessenberg.block_size and
+ *     .blocking_threshold (the blocked reduction), the other fields of schur (no aggressive early deflation yet),
+ *     evd_from_schur.  `par` and `mem` are ignored.
+ * --------------------------------------------------------------------------------------------- */
+FAER_HIP_API size_t faer_hip_default_relative_cost_estimate_of_shift_chase_to_matmul(size_t matrix_dimension, size_t active_block_dimension);
+FAER_HIP_API FaerGeneralizedHessenbergParams libfaer_v0_23_GeneralizedHessenbergParams_f64(void);
+FAER_HIP_API FaerGeneralizedHessenbergParams libfaer_v0_23_GeneralizedHessenbergParams_f32(void);
+FAER_HIP_API FaerGeneralizedSchurParams libfaer_v0_23_GeneralizedSchurParams_f64(void);
+FAER_HIP_API FaerGeneralizedSchurParams libfaer_v0_23_GeneralizedSchurParams_f32(void);
+FAER_HIP_API FaerGevdParams libfaer_v0_23_GevdParams_f64(void);
+FAER_HIP_API FaerGevdParams libfaer_v0_23_GevdParams_f32(void);
+FAER_HIP_API FaerLayout libfaer_v0_23_generalized_evd_scratch_f64(size_t dim, FaerComputeEigenvectors compute_left, FaerComputeEigenvectors compute_right, FaerPar par, FaerGevdParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_generalized_evd_scratch_f32(size_t dim, FaerComputeEigenvectors compute_left, FaerComputeEigenvectors compute_right, FaerPar par, FaerGevdParams params);
+FAER_HIP_API FaerGevdStatus libfaer_v0_23_generalized_evd_f64(FaerMatMut A, FaerMatMut B, FaerMatMut UL, FaerMatMut UR, FaerVecMut alpha, FaerVecMut alpha_im, FaerVecMut beta, FaerPar par, FaerMemAlloc mem, FaerGevdParams params);
+FAER_HIP_API FaerGevdStatus libfaer_v0_23_generalized_evd_f32(FaerMatMut A, FaerMatMut B, FaerMatMut UL, FaerMatMut UR, FaerVecMut alpha, FaerVecMut alpha_im, FaerVecMut beta, FaerPar par, FaerMemAlloc mem, FaerGevdParams params);
 #endif /* FAER_HIP_NO_FFI_PROTOTYPES */
 /* debug / measurement: {sweeps, window steps, leaf launches, state read-backs} of the calling thread's last evd; the window edge W */
 FAER_HIP_API void faer_hip_debug_evd_last_counts(long out[4]);
 FAER_HIP_API size_t faer_hip_evd_window_edge(FaerHipDType dtype);
+/* {multishift sweeps, window steps, leaf launches, state read-backs, infinite eigenvalues deflated} of the calling thread's last
+ * generalized_evd; the window edge W (64 for f64, 96 for f32) */
+FAER_HIP_API void faer_hip_debug_gevd_last_counts(long out[5]);
+FAER_HIP_API size_t faer_hip_gevd_window_edge(FaerHipDType dtype);
 /* ---------------------------------------------------------------------------------------------
  * 3. Runtime control (new: the reference has no device).
  * --------------------------------------------------------------------------------------------- */
