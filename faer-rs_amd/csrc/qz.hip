@@ -166,7 +166,7 @@ __global__ __launch_bounds__(QZ_THREADS) void gevd_shift_kernel(const T *h, cons
 	}
 	__syncthreads();
 	if (threadIdx.x == 0) {
-		qz_sweep_shifts(h, n, t, n, istop, ns, exceptional != 0, err, (const T *) ev[0], (const T *) ev[1], (const T *) ev[2], ev[3], ev[4]);
+		qz_sweep_shifts(h, n, t, n, istop, ns, exceptional != 0, err, (const T *) ev[0], (const T *) ev[1], (const T *) ev[2], norms[0], norms[1], ev[3], ev[4]);
 		for (int i = 0; i < ns; ++i) {
 			sr[i] = ev[3][i];
 			si[i] = ev[4][i];
@@ -176,8 +176,8 @@ __global__ __launch_bounds__(QZ_THREADS) void gevd_shift_kernel(const T *h, cons
 
 // one window step: the ws x ws window at row w0 and two identities in LDS, a chain of nb bulges introduced, chased or run off
 template <typename T>
-__global__ __launch_bounds__(QZ_THREADS) void gevd_window_kernel(T *h, T *t, long n, long w0, long ws, long ilo, long ihi, int nb, const T *sr, const T *si, long A, long B,
-								  T *u, T *v)
+__global__ __launch_bounds__(QZ_THREADS) void gevd_window_kernel(T *h, T *t, long n, long w0, long ws, long ilo, long ihi, int nb, const T *sr, const T *si, const T *norms,
+								  long A, long B, T *u, T *v)
 {
 	__shared__ T ls[2][qz_w<T>()];
 	for (int i = threadIdx.x; i < 2 * nb; i += blockDim.x) {
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(QZ_THREADS) void gevd_window_kernel(T *h, T *t, lon
 		ls[1][i] = si[i];
 	}
 	const Pencil<T> p = qz_load_window(h, t, n, w0, ws, true);
-	qz_window_chase(DevGroup{}, p, w0, ilo, ihi, nb, (const T *) ls[0], (const T *) ls[1], A, B);
+	qz_window_chase(DevGroup{}, p, w0, ilo, ihi, nb, (const T *) ls[0], (const T *) ls[1], norms[0], norms[1], A, B);
 	qz_store_window(p, h, t, n, w0, u, v);
 }
 
@@ -290,8 +290,8 @@ template <typename T> struct DeviceQz {
 	}
 	void window(long w0, long ws, long ilo, long ihi, int nb, long A, long B)
 	{
-		hipLaunchKernelGGL(gevd_window_kernel<T>, dim3(1), dim3(QZ_THREADS), qz_lds<T>(), s, H.p, Tm.p, n, w0, ws, ilo, ihi, nb, (const T *) sr, (const T *) si, A, B, u,
-				   v);
+		hipLaunchKernelGGL(gevd_window_kernel<T>, dim3(1), dim3(QZ_THREADS), qz_lds<T>(), s, H.p, Tm.p, n, w0, ws, ilo, ihi, nb, (const T *) sr, (const T *) si, (const T *) norms, A,
+				   B, u, v);
 		FH_HIP(hipGetLastError());
 		off_block((idx_t) w0, (idx_t) ws);
 	}

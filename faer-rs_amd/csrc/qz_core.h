@@ -231,9 +231,11 @@ template <typename T, typename G> SC_HD void double_step(const G &g, const Penci
 // One window step of a multishift sweep (the counterpart of schur_core.h's window_chase, same geometry): p is the ws x ws window
 // of (H, T) at global row w0 with its two accumulators (identities on entry).  Bulge b of nb uses the shifts (sr, si)[2 b],
 // [2 b + 1] and takes the steps whose column index k (global) runs over [A - 3 b, B - 3 b), clipped to [ilo - 1, ihi - 2):
-// k == ilo - 1 introduces it at the top of the active block [ilo, ihi), the last two rows let it run off.
+// k == ilo - 1 introduces it at the top of the active block [ilo, ihi), the last two rows let it run off.  The shifts are
+// eigenvalues of (H / sa, T / sb), sa = |H|_F, sb = |T|_F of the whole pair (qz_sweep_shifts), and the first column of the bulge
+// is formed in those units: of order one whatever the scales of A and B, and unchanged when either is scaled by a power of two.
 template <typename T, typename G>
-SC_HD void qz_window_chase(const G &g, const Pencil<T> &p, long w0, long ilo, long ihi, int nb, const T *sr, const T *si, long A, long B)
+SC_HD void qz_window_chase(const G &g, const Pencil<T> &p, long w0, long ilo, long ihi, int nb, const T *sr, const T *si, T sa, T sb, long A, long B)
 {
 	const long ilast = sc_min(ihi - w0, p.n) - 1;
 	for (int b = 0; b < nb; ++b) {
@@ -250,7 +252,7 @@ SC_HD void qz_window_chase(const G &g, const Pencil<T> &p, long w0, long ilo, lo
 				T v1 = 0, v2 = 0, v3 = 0;
 				g.sync();
 				if (intro)
-					shift_vector(p, j, s1r + s2r, s1r * s2r - s1i * s2i, (T) 1, (T) 1, v1, v2, v3);
+					shift_vector(p, j, s1r + s2r, s1r * s2r - s1i * s2i, sa, sb, v1, v2, v3);
 				double_step(g, p, j, ilast, !intro, v1, v2, v3);
 			} else {
 				single_step(g, p, j, ilast, true, (T) 1, (T) 0);
@@ -260,12 +262,22 @@ SC_HD void qz_window_chase(const G &g, const Pencil<T> &p, long w0, long ilo, lo
 	g.sync();
 }
 
-// The ns shifts of a sweep on the block that ends at row istop (exclusive) of the n x n pair (h, t) in global memory, from the
-// eigenvalues (ar + i ai) / be of its trailing ns x ns sub-pencil (err != 0: they are not all there), paired as
-// schur_core.h pairs them.  An infinite or missing eigenvalue, or `exceptional`, gives the ad hoc shifts
-// h(i, i - 1) / t(i - 1, i - 1) + h(i, i) / t(i, i) of the trailing rows.  One thread.
-template <typename T> SC_HD void qz_sweep_shifts(const T *h, long ldh, const T *t, long ldt, long istop, int ns, bool exceptional, long err, const T *ar, const T *ai,
-						 const T *be, T *wr, T *wi)
+// (the same in the units of H and T themselves, sa = sb = 1, for a pair near unit scale: a host program that holds no norms)
+template <typename T, typename G>
+SC_HD void qz_window_chase(const G &g, const Pencil<T> &p, long w0, long ilo, long ihi, int nb, const T *sr, const T *si, long A, long B)
+{
+	qz_window_chase(g, p, w0, ilo, ihi, nb, sr, si, (T) 1, (T) 1, A, B);
+}
+
+// The ns shifts of a sweep on the block that ends at row istop (exclusive) of the n x n pair (h, t) in global memory: the
+// eigenvalues ((ar + i ai) / sa) / (be / sb) of its trailing ns x ns sub-pencil in units of sa = |H|_F, sb = |T|_F, that is the
+// eigenvalues of (H / sa, T / sb) (err != 0: they are not all there), paired as schur_core.h pairs them.  An infinite or missing
+// eigenvalue, or `exceptional`, gives the ad hoc shifts h(i, i - 1) / t(i - 1, i - 1) + h(i, i) / t(i, i) of the trailing rows
+// in the same units.  No quotient of an entry of H by an entry of T is formed unscaled: lambda itself need not be representable.
+// One thread.
+template <typename T>
+SC_HD void qz_sweep_shifts(const T *h, long ldh, const T *t, long ldt, long istop, int ns, bool exceptional, long err, const T *ar, const T *ai, const T *be,
+			   T sa, T sb, T *wr, T *wi)
 {
 	bool bad = exceptional || err != 0;
 	for (int i = 0; i < ns && !bad; ++i)
@@ -273,15 +285,23 @@ template <typename T> SC_HD void qz_sweep_shifts(const T *h, long ldh, const T *
 	for (int i = 0; i < ns; ++i) {
 		const long r = istop - ns + i;
 		if (bad) {
-			wr[i] = h[r + (r - 1) * ldh] / t[(r - 1) + (r - 1) * ldt] + h[r + r * ldh] / t[r + r * ldt];
+			wr[i] = (h[r + (r - 1) * ldh] / sa) / (t[(r - 1) + (r - 1) * ldt] / sb) + (h[r + r * ldh] / sa) / (t[r + r * ldt] / sb);
 			wi[i] = 0;
 		} else {
-			wr[i] = ar[i] / be[i];
-			wi[i] = ai[i] / be[i];
+			wr[i] = (ar[i] / sa) / (be[i] / sb);
+			wi[i] = (ai[i] / sa) / (be[i] / sb);
 		}
 	}
 	const long e = istop - 1;
-	pair_shifts(wr, wi, ns, h[e + e * ldh] / t[e + e * ldt]);
+	pair_shifts(wr, wi, ns, (h[e + e * ldh] / sa) / (t[e + e * ldt] / sb));
+}
+
+// (in the units of H and T themselves, to go with the window chase in those units)
+template <typename T>
+SC_HD void qz_sweep_shifts(const T *h, long ldh, const T *t, long ldt, long istop, int ns, bool exceptional, long err, const T *ar, const T *ai, const T *be,
+			   T *wr, T *wi)
+{
+	qz_sweep_shifts(h, ldh, t, ldt, istop, ns, exceptional, err, ar, ai, be, (T) 1, (T) 1, wr, wi);
 }
 
 // The QZ iteration on the Hessenberg-triangular pair p (the whole matrix is the active block): on return H is quasi upper
@@ -407,11 +427,10 @@ SC_HD long qz_unblocked(const G &g, const Pencil<T> &p, T *ar, T *ai, T *be, T a
 		++iiter;
 		g.sync();
 		const long l = ilast - 1;
-		T s1, wr = 0, sa = 1, sb = 1, w1 = 0, w2 = 0, wi = 0;
+		T wr = 0, sa = 1, sb = 1, w1 = 0, w2 = 0, wi = 0;
 		bool single = true;
 		if (iiter % 10 == 0) {
 			eshift += ldc(p.H(ilast, l)) / ldc(p.B(l, l));
-			s1 = 1;
 			wr = eshift;
 		} else {
 			lag2(ldc(p.H(l, l)), ldc(p.H(l, ilast)), ldc(p.H(ilast, l)), ldc(p.H(ilast, ilast)), ldc(p.B(l, l)), ldc(p.B(l, ilast)),
@@ -420,13 +439,11 @@ SC_HD long qz_unblocked(const G &g, const Pencil<T> &p, T *ar, T *ai, T *be, T a
 				const T hl = ldc(p.H(ilast, ilast)), tl = ldc(p.B(ilast, ilast));
 				if (sc_abs(w1 * sa * (tl / sb) - hl) > sc_abs(w2 * sa * (tl / sb) - hl))
 					w1 = w2;
-				// the shift w1 sa / sb as the pair (s1, wr): s1 H and wr T scale alike when A and B are scaled by powers of two
-				s1 = sb;
-				wr = w1 * sa;
-			} else {
+				// the shift w1 of (H / sa, T / sb): the first column of the sweep is formed in those units, where no product
+				// of a scale of H by a scale of T can leave the range
+				wr = w1;
+			} else
 				single = false;
-				s1 = 0;
-			}
 		}
 		if (!single && ifirst + 1 == ilast) {
 			// a 2 x 2 block with a conjugate pair: T <- its singular values (the role of svd_triu_2x2), then (alpha, beta)
@@ -474,7 +491,7 @@ SC_HD long qz_unblocked(const G &g, const Pencil<T> &p, T *ar, T *ai, T *be, T a
 			cnt[QC_SWEEPS] += 1;
 		if (single) {
 			T c, s, r;
-			givens(s1 * ldc(p.H(ifirst, ifirst)) - wr * ldc(p.B(ifirst, ifirst)), s1 * ldc(p.H(ifirst + 1, ifirst)), c, s, r);
+			givens(ldc(p.H(ifirst, ifirst)) / sa - wr * (ldc(p.B(ifirst, ifirst)) / sb), ldc(p.H(ifirst + 1, ifirst)) / sa, c, s, r);
 			for (long j = ifirst; j < ilast; ++j)
 				single_step(g, p, j, ilast, j > ifirst, c, s);
 			continue;
@@ -532,8 +549,9 @@ SC_HD void gevec_block(const G &g, const T *sp, long srs, long scs, const T *pp,
 	const T ascale = 1 / sc_max(snorm, safmin), bscale = 1 / sc_max(pnorm, safmin);
 	const T alr = ar[top * es], ali = pair ? sc_abs(ai[top * es]) * imsign : (T) 0, bet = be[top * es];
 	const T temp = 1 / sc_max(sc_max((sc_abs(alr) + sc_abs(ali)) * ascale, sc_abs(bet) * bscale), safmin);
-	const T acoef = (temp * bet) * ascale * bscale;
-	const Cx<T> bc{(temp * alr) * ascale * bscale, (temp * ali) * ascale * bscale};
+	// (beta by bscale and alpha by ascale first, as the reference: each is of order one then; beta ascale alone can underflow)
+	const T acoef = ((temp * bet) * bscale) * ascale;
+	const Cx<T> bc{((temp * alr) * ascale) * bscale, ((temp * ali) * ascale) * bscale};
 	const T dmin = sc_max(sc_max(ulp * sc_abs(acoef) * snorm, ulp * cx_abs1(bc) * pnorm), safmin);
 	const T big = 1 / sc_sqrt(safmin);
 	Cx<T> xa{1, 0}, xb{1, 0}; // components top, k of the block

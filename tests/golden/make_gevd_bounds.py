@@ -19,10 +19,19 @@ def sizes(dtype):
     return sorted(set([1, 2, 3, W - 1, W, W + 1, 2 * W + 3, 3 * W + 5] + gc.HOST_SIZES))
 
 
+def vector_sizes(dtype):
+    """sizes of gc.VECTOR_KINDS: the size at which the guard fires, the host's 15 and 35, the GPU's W + 1 for the rotations"""
+    return sorted({gc.GUARD_N, 15, 35, EDGES[np.dtype(dtype)] + 1})
+
+
+def cases(dtype):
+    return gc.all_cases(sizes(dtype)) + gc.vector_cases(vector_sizes(dtype))
+
+
 def main():
     out, arrays = {}, {}
     for dtype in gc.DTYPES:
-        for kind, n in gc.all_cases(sizes(dtype)):
+        for kind, n in cases(dtype):
             key = gc._key(kind, n, dtype)
             out[key], arr = gc.encode(gc._compute(kind, n, dtype))
             arrays[key] = arr

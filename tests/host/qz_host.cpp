@@ -6,6 +6,7 @@
 //      go to the leaf, larger ones take multishift sweeps in windows of edge W.  cap: iteration cap of a scan or a leaf
 //      (0: 30 max(10, n)).  QZ_HOST_NS in the environment: the shift count the driver is given (default 4).
 // out: doubles: status, sweeps, infinite deflations, leaves, window steps; alpha_re, alpha_im, beta (n each); UR, UL, S, P, Q, Z (n x n each).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -119,12 +120,12 @@ template <typename T> struct HostQz {
 		sr.assign((size_t) ns, 0);
 		si.assign((size_t) ns, 0);
 		qz_sweep_shifts((const T *) p.h, p.ldh, (const T *) p.t, p.ldt, ihi, ns, exceptional, err, (const T *) a.data(), (const T *) b.data(),
-				(const T *) c.data(), sr.data(), si.data());
+				(const T *) c.data(), anorm, bnorm, sr.data(), si.data());
 	}
 	void window(long w0, long ws, long ilo, long ihi, int nb, long A, long B)
 	{
 		Pencil<T> l = local(w0, ws);
-		qz_window_chase(g, l, w0, ilo, ihi, nb, (const T *) sr.data(), (const T *) si.data(), A, B);
+		qz_window_chase(g, l, w0, ilo, ihi, nb, (const T *) sr.data(), (const T *) si.data(), anorm, bnorm, A, B);
 		off_block(w0, ws);
 	}
 };
@@ -142,12 +143,17 @@ template <typename T> static int run(long n, long edge, long cap, const std::vec
 	fh::schur::HostGroup g;
 	Pencil<T> p{a.data(), n, b.data(), n, n, q.data(), n, z.data(), n};
 	hessenberg_triangular(g, p);
-	double sa = 0, sb = 0;
+	// Frobenius norms, scaled by the largest entry so that the squares stay in range (as gevd_norms_kernel of csrc/qz.hip)
+	double ma = 0, mb = 0, sa = 0, sb = 0;
 	for (size_t i = 0; i < nn; ++i) {
-		sa += (double) a[i] * (double) a[i];
-		sb += (double) b[i] * (double) b[i];
+		ma = std::fmax(ma, std::fabs((double) a[i]));
+		mb = std::fmax(mb, std::fabs((double) b[i]));
 	}
-	const T anorm = (T) std::sqrt(sa), bnorm = (T) std::sqrt(sb);
+	for (size_t i = 0; i < nn; ++i) {
+		sa += ma > 0 ? ((double) a[i] / ma) * ((double) a[i] / ma) : 0;
+		sb += mb > 0 ? ((double) b[i] / mb) * ((double) b[i] / mb) : 0;
+	}
+	const T anorm = (T) (ma * std::sqrt(sa)), bnorm = (T) (mb * std::sqrt(sb));
 	HostQz<T> hq;
 	hq.n = n;
 	hq.W = edge;

@@ -1,5 +1,6 @@
 """generalized_evd on the GPU: every kind of tests/gevd_cases.py at n in {1, 2, 3, W - 1, W, W + 1, 2 W + 3, 3 W + 5} in both dtypes
-under both verdicts (W = gevd_window_edge: up to W rows one LDS-resident leaf, beyond it multishift sweeps in windows), and the standing
+under both verdicts (W = gevd_window_edge: up to W rows one LDS-resident leaf, beyond it multishift sweeps in windows), the `random`
+kind as (A 2^ka, B 2^kb) at every row of gc.RANGE_SCALES, the kinds built for the eigenvector stage (gc.VECTOR_KINDS), and the standing
 families: wanted / unwanted vector sets, host operands, padded / offset / row-major views, the poisoned scratch pool, a
 non-blocking caller stream, non-finite inputs, custom shift counts, the counters."""
 import ctypes as C
@@ -82,6 +83,102 @@ def test_kinds_pass_both_verdicts(kind, n, dtype):
         ref = np.linalg.eigvals(a.astype(np.float64))
         d = np.abs(lam[:, None] - ref[None, :]).min(axis=1).max()
         assert d <= 1e3 * n * gc.eps_of(dtype) * np.linalg.norm(a.astype(np.float64))
+
+
+def range_sizes(dtype):
+    W = WEDGE[np.dtype(dtype)]
+    return [W - 1, W + 1, 2 * W + 3]
+
+
+_UNSCALED = {}
+
+
+def unscaled_run(F, n, dtype, vectors=True):
+    """the result on the `random` pair itself, once per size and dtype"""
+    key = (n, np.dtype(dtype).name, vectors)
+    if key not in _UNSCALED:
+        a, b = gc.generate("random", n, dtype)
+        _UNSCALED[key] = run(F, a, b, vectors, vectors) + (F.debug_gevd_last_counts(),)
+    return _UNSCALED[key]
+
+
+def qr_fast_path(b):
+    nz = np.abs(b[b != 0]).astype(np.float64)
+    return bool(((nz >= 1e-120) & (nz <= 1e120)).all())
+
+
+def range_row(F, n, dtype, ka, kb, vectors):
+    """(A 2^ka, B 2^kb): GEVD_OK, the counters, both verdicts on unscaled quantities, and the unscaled call's alpha 2^ka,
+    beta 2^kb and vectors bit for bit"""
+    W = WEDGE[np.dtype(dtype)]
+    _, _, a, b = gc.range_generate(n, dtype, ka, kb)
+    tag, al, ai, be, ul, ur = run(F, a, b, vectors, vectors)
+    cnt = F.debug_gevd_last_counts()
+    print(f"random n={n} {np.dtype(dtype).name} 2^({ka}, {kb}): tag {tag}, {cnt}")
+    assert tag == F.GEVD_OK
+    gc.range_check(n, dtype, ka, kb, al, ai, be, ur, ul)
+    assert (be >= 0).all()
+    if n <= W:
+        assert cnt["window_steps"] == 0 and cnt["sweeps"] == 0
+    else:
+        assert cnt["sweeps"] > 0 and cnt["window_steps"] > cnt["sweeps"]
+    assert cnt["readbacks"] <= cnt["sweeps"] + cnt["leaves"] + READBACK_CONSTANT
+    tag0, al0, ai0, be0, ul0, ur0, cnt0 = unscaled_run(F, n, dtype, vectors)
+    assert tag0 == F.GEVD_OK and cnt == cnt0
+    exact = [np.array_equal(np.ldexp(al0, ka), al), np.array_equal(np.ldexp(ai0, ka), ai), np.array_equal(np.ldexp(be0, kb), be)]
+    if vectors:
+        exact += [np.array_equal(ul0, ul), np.array_equal(ur0, ur)]
+    print(f"random n={n} {np.dtype(dtype).name} 2^({ka}, {kb}): bit-exact alpha, alpha_im, beta, UL, UR: {exact}")
+    # Stages 1 to 3 scale exactly at every row (tests/test_qz_host.py).  Stage 0, the QR of B, has two paths in fp64: a nonzero
+    # entry of B outside [1e-120, 1e120] takes the general one (copy_guard_kernel of csrc/qr.hip), whose norms round differently,
+    # so there the whole call is compared bit for bit only with a B on the same path
+    if np.dtype(dtype) == np.float32 or qr_fast_path(b):
+        assert all(exact)
+
+
+RANGE = [(n, dtype, group, ka, kb) for dtype in DTYPES for n in range_sizes(dtype) for group, ka, kb in gc.range_rows(dtype)]
+
+
+@pytest.mark.parametrize("n,dtype,group,ka,kb", RANGE, ids=[f"{n}-{np.dtype(d).name}-{g}-{ka}-{kb}" for n, d, g, ka, kb in RANGE])
+def test_range_rows(n, dtype, group, ka, kb):
+    """every row of gc.RANGE_SCALES at n = W - 1 (one leaf), W + 1 and 2 W + 3 (windows)"""
+    assert gc.range_representable(n, dtype, ka, kb)
+    range_row(init_gpu(), n, dtype, ka, kb, True)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f64", "f32"])
+def test_range_row_eigenvalues_only(dtype):
+    """the widest row apart, neither vector set wanted: lambda itself is not representable, (alpha, beta) is"""
+    ka, kb = gc.RANGE_SCALES[np.dtype(dtype)]["beyond"][2]
+    range_row(init_gpu(), WEDGE[np.dtype(dtype)] + 1, dtype, ka, kb, False)
+
+
+VECTOR = [(kind, gc.GUARD_N if kind in gc.TRIANGLE_KINDS else WEDGE[np.dtype(dtype)] + 1, dtype) for dtype in DTYPES for kind in gc.VECTOR_KINDS]
+
+
+@pytest.mark.parametrize("kind,n,dtype", VECTOR, ids=[f"{k}-{n}-{np.dtype(d).name}" for k, n, d in VECTOR])
+def test_vector_kinds(kind, n, dtype):
+    """the kinds built for gevd_vec_kernel: the overflow rescale (graded_triangular_pair at the size where it fires), the pivot floor
+    at every divisor (jordan_pair), the vectors of infinite eigenvalues (infinite_in_triangle), and their rotations at W + 1;
+    triangular pairs take zero sweeps and keep their diagonals (gc.check asserts alpha and beta exactly)"""
+    F = init_gpu()
+    a, b = gc.generate(kind, n, dtype)
+    tag, al, ai, be, ul, ur = run(F, a, b)
+    cnt = F.debug_gevd_last_counts()
+    print(f"{kind} n={n} {np.dtype(dtype).name}: tag {tag}, {cnt}")
+    assert tag == F.GEVD_OK
+    for x in (al, ai, be, ul, ur):
+        assert np.isfinite(x).all()
+    # (the QR of a singular triangular B is another triangle: the diagonals of infinite_in_triangle are asserted on the host alone)
+    gc.check(kind, n, dtype, a, b, al, ai, be, ur, ul, stage0_identity=kind != "infinite_in_triangle")
+    assert (be >= 0).all()
+    if kind == "infinite_in_triangle":
+        assert cnt["infinite_deflations"] >= len(gc.infinite_rows(n))
+    if kind in gc.TRIANGLE_KINDS:
+        assert cnt["sweeps"] == 0 and cnt["window_steps"] == 0
+    elif kind != "rotated_infinite_in_triangle":  # (three infinite eigenvalues deflate first: the block left may fit one leaf)
+        assert cnt["sweeps"] > 0 and cnt["window_steps"] > cnt["sweeps"]
+    assert cnt["readbacks"] <= cnt["sweeps"] + cnt["leaves"] + READBACK_CONSTANT
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f64", "f32"])

@@ -2,7 +2,8 @@
 runs the Hessenberg-triangular reduction, the sweep driver (scan, shifts, window steps, leaves) and the eigenvectors of a pair whose B is triangular (stage 0, the QR of
 B, is numpy's here).  No GPU.  Every kind of tests/gevd_cases.py at n = 1, 2, 3, 15, 16, 17, 35 with edge 16, under both verdicts;
 the decomposition itself (A = Q S Z^T, B = Q P Z^T, the form of S and P); the iteration cap; the deflation of an infinite
-eigenvalue at the bottom and in the interior of the pair."""
+eigenvalue at the bottom and in the interior of the pair; the `random` kind as (A 2^ka, B 2^kb) at every row of gc.RANGE_SCALES,
+n = 15 (one leaf), 17 and 35 (windows); the kinds built for the eigenvector stage (gc.VECTOR_KINDS)."""
 import os
 import shutil
 import subprocess
@@ -82,6 +83,61 @@ def test_kinds_pass_both_verdicts(exe, tmp_path, kind, n, dtype):
     if kind == "identity_b":
         lam = np.sort_complex((r["alpha"].astype(np.float64) + 1j * r["alpha_im"]) / r["beta"])
         assert np.abs(lam - np.sort_complex(np.linalg.eigvals(a.astype(np.float64)))).max() <= 1e3 * n * e * np.linalg.norm(a)
+
+
+_UNSCALED = {}
+
+
+def unscaled_run(exe, tmp_path, n, dtype):
+    """the result on the `random` pair itself, once per size and dtype"""
+    key = (n, np.dtype(dtype).name)
+    if key not in _UNSCALED:
+        _UNSCALED[key] = run(exe, tmp_path, *gc.generate("random", n, dtype), dtype)
+    return _UNSCALED[key]
+
+
+RANGE = [(n, dtype, group, ka, kb) for dtype in gc.DTYPES for n in gc.RANGE_HOST_SIZES for group, ka, kb in gc.range_rows(dtype)]
+
+
+@pytest.mark.parametrize("n,dtype,group,ka,kb", RANGE, ids=[f"{n}-{np.dtype(d).name}-{g}-{ka}-{kb}" for n, d, g, ka, kb in RANGE])
+def test_range_rows(exe, tmp_path, n, dtype, group, ka, kb):
+    """(A 2^ka, B 2^kb) at the ends of the range: convergence, both verdicts on unscaled quantities, and alpha 2^ka, beta 2^kb and
+    the vectors of the unscaled pair bit for bit.  Beyond sqrt(max) the square of a shift lambda is not representable: shifts
+    carried as lambda itself end a block of more than EDGE rows at the iteration cap."""
+    _, _, a, b = gc.range_generate(n, dtype, ka, kb)
+    r = run(exe, tmp_path, a, b, dtype)
+    assert r["status"] == 0, (r["status"], r["sweeps"])
+    assert (r["sweeps"] > 0 and r["window_steps"] > r["sweeps"]) if n > EDGE else r["sweeps"] == 0
+    gc.range_check(n, dtype, ka, kb, r["alpha"], r["alpha_im"], r["beta"], r["ur"].astype(dtype), r["ul"].astype(dtype))
+    r0 = unscaled_run(exe, tmp_path, n, dtype)
+    assert r["sweeps"] == r0["sweeps"] and r["window_steps"] == r0["window_steps"] and r["leaves"] == r0["leaves"]
+    assert np.array_equal(np.ldexp(r0["alpha"], ka), r["alpha"]) and np.array_equal(np.ldexp(r0["alpha_im"], ka), r["alpha_im"])
+    assert np.array_equal(np.ldexp(r0["beta"], kb), r["beta"])
+    assert np.array_equal(r0["ur"], r["ur"]) and np.array_equal(r0["ul"], r["ul"])
+
+
+def vector_sizes(kind):
+    """the size at which the guard fires, or 15 and 35 where no firing is needed"""
+    return [n for n in ([gc.GUARD_N] if kind.endswith("graded_triangular_pair") else [15, 35, gc.GUARD_N]) if gc.exists(kind, n)]
+
+
+VECTOR = [(kind, n, dtype) for dtype in gc.DTYPES for kind in gc.VECTOR_KINDS for n in vector_sizes(kind)]
+
+
+@pytest.mark.parametrize("kind,n,dtype", VECTOR, ids=[f"{k}-{n}-{np.dtype(d).name}" for k, n, d in VECTOR])
+def test_vector_kinds(exe, tmp_path, kind, n, dtype):
+    """the kinds built for the back substitution: the overflow rescale, the pivot floor at every divisor, the vectors of
+    infinite eigenvalues; triangular pairs take zero sweeps and keep their diagonals (gc.check asserts alpha and beta exactly)"""
+    a, b = gc.generate(kind, n, dtype)
+    r = run(exe, tmp_path, a, b, dtype, pre_qr=kind.startswith("rotated_"))
+    assert r["status"] == 0
+    for x in ("alpha", "alpha_im", "beta", "ur", "ul"):
+        assert np.isfinite(r[x]).all()
+    gc.check(kind, n, dtype, a, b, r["alpha"], r["alpha_im"], r["beta"], r["ur"].astype(dtype), r["ul"].astype(dtype))
+    if kind in gc.TRIANGLE_KINDS:
+        assert r["sweeps"] == 0 and r["window_steps"] == 0
+    if kind == "infinite_in_triangle":
+        assert r["infinite"] == len(gc.infinite_rows(n))
 
 
 def test_iteration_cap_reports_no_convergence(exe, tmp_path):
