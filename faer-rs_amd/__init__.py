@@ -674,6 +674,75 @@ def gevd_window_edge(dtype):
     return int(f(C.c_int(DTYPE_F64 if np.dtype(dtype) == np.float64 else DTYPE_F32)))
 
 
+def llt_rank_r_update_clobber(l, w, alpha, raise_on_error=True):
+    """faer::linalg::cholesky::llt::update::rank_r_update_clobber (llt/update.rs:360): the factor in the lower triangle of `l` (n x n)
+    becomes that of A + w diag(alpha) w^T (`w` n x r, `alpha` 1-D with r entries; a negative alpha downdates).  `w` and `alpha` are
+    clobbered.  Each operand is a numpy array or a device tensor on its own.  Raises LltError(index) like Err(NonPositivePivot{index});
+    with raise_on_error=False returns the index instead (None: Ok)."""
+    suf, _, _ = _dtype_suffix(l)
+    fn = getattr(lib(), f"faer_hip_llt_rank_r_update_clobber_{suf}")
+    fn.restype = LltStatus
+    st = fn(_mat(l, MatMut), _mat(w, MatMut), _vec(alpha, VecMut))
+    if st.tag == 0:
+        return None
+    if st.tag != 1:
+        raise RuntimeError("LltStatus::Unknown")
+    if raise_on_error:
+        raise LltError(st.value)
+    return int(st.value)
+
+
+def ldlt_rank_r_update_clobber(ld, w, alpha):
+    """faer::linalg::cholesky::ldlt::update::rank_r_update_clobber (ldlt/update.rs:376): the same for L D L^T packed as
+    ldlt_factor_in_place leaves it (unit lower L strictly below the diagonal of `ld`, D on it)"""
+    suf, _, _ = _dtype_suffix(ld)
+    fn = getattr(lib(), f"faer_hip_ldlt_rank_r_update_clobber_{suf}")
+    fn.restype = None
+    fn(_mat(ld, MatMut), _mat(w, MatMut), _vec(alpha, VecMut))
+    return ld
+
+
+def ldlt_delete_rows_and_cols_clobber(ld, indices, index_dtype=np.uint64):
+    """faer::linalg::cholesky::ldlt::update::delete_rows_and_cols_clobber (ldlt/update.rs:417): the leading (n - r)^2 block of `ld`
+    receives the factors of A without the rows and columns `indices`; the trailing r rows are unspecified.  Returns the indices as
+    the call left them: sorted, in an array of `index_dtype`."""
+    suf, _, _ = _dtype_suffix(ld)
+    it = "u64" if np.dtype(index_dtype) == np.uint64 else "u32"
+    idx = np.array(indices, dtype=np.uint64 if it == "u64" else np.uint32).ravel()
+    fn = getattr(lib(), f"faer_hip_ldlt_delete_rows_and_cols_clobber_{it}_{suf}")
+    fn.restype = None
+    fn(_mat(ld, MatMut), SliceMut(idx.ctypes.data if idx.size else None, idx.shape[0]), PAR_SEQ, MemAlloc(None, 0))
+    return idx
+
+
+def ldlt_delete_rows_and_cols_clobber_scratch(dim, n_removed, dtype=np.float64):
+    """(len_bytes, align_bytes) of the reference's scratch figure: dim * n_removed + n_removed scalars"""
+    fn = getattr(lib(), f"faer_hip_ldlt_delete_rows_and_cols_clobber_scratch_{'f64' if np.dtype(dtype) == np.float64 else 'f32'}")
+    fn.restype = Layout
+    lay = fn(C.c_size_t(dim), C.c_size_t(n_removed))
+    return int(lay.len_bytes), int(lay.align_bytes)
+
+
+def debug_chol_update_last():
+    """{column blocks, tail launches, chunks of W per block, host synchronisations inside the block loop} of the calling thread's last
+    Cholesky update or deletion"""
+    out = (C.c_long * 4)()
+    lib().faer_hip_debug_chol_update_last(out)
+    return dict(zip(("blocks", "tail_launches", "chunks", "loop_syncs"), (int(v) for v in out)))
+
+
+def debug_chol_update_diag_only(on):
+    """measurement aid: True = only the diagonal kernels of the Cholesky update run (its serial chain; the factor is wrong)"""
+    lib().faer_hip_debug_chol_update_diag_only(C.c_int(1 if on else 0))
+
+
+def chol_update_shape(dtype):
+    """(NB, RC): columns per block and columns of W per chunk of the Cholesky update kernels.  Needs no GPU."""
+    out = (C.c_size_t * 2)()
+    lib().faer_hip_chol_update_shape(C.c_int(DTYPE_F64 if np.dtype(dtype) == np.float64 else DTYPE_F32), out)
+    return int(out[0]), int(out[1])
+
+
 def svd(a, s, u=None, v=None, params=None, par=PAR_SEQ):
     """faer::linalg::svd::svd (svd/mod.rs:530): singular values of `a` (m x n, never written) in nonincreasing order into
     the 1-D `s` (min(m, n) entries); with `u` (m x min(m, n) or m x m) / `v` (n x min(m, n) or n x n) the left / right

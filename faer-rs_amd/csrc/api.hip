@@ -1,6 +1,7 @@
 // extern "C" surface of libfaer_hip.so (see include/faer_hip.h for the contract and the reference
 // citations of every entry point).  This file only validates shapes, stages host operands and forwards
 // to the device drivers; there is deliberately no CPU compute path here.
+#include <algorithm>
 #include <atomic>
 #include <limits>
 
@@ -731,6 +732,45 @@ FaerGevdStatus gevd_api(FaerMatMut Am, FaerMatMut Bm, FaerMatMut UL, FaerMatMut 
 	}
 	st.tag = r == 0 ? FaerGevdStatus_Ok : FaerGevdStatus_NoConvergence;
 	return st;
+}
+
+// cholesky/llt/update.rs:360-379 and cholesky/ldlt/update.rs:376-400
+template <typename T> FaerLltStatus chol_update_api(FaerMatMut L, FaerMatMut W, FaerVecMut alpha, bool ldlt)
+{
+	const size_t n = L.nrows, r = W.ncols;
+	FH_CHECK(L.ncols == n && W.nrows == n && alpha.len == r, "rank_r_update: L must be n x n, W n x r, alpha must have r entries");
+	FaerLltStatus st;
+	memset(&st, 0, sizeof(st));
+	st.tag = FaerLltStatus_Ok;
+	if (n == 0 || r == 0)
+		return st;
+	ctx().ensure_device();
+	const long res = chol_rank_update<T>(view<T>(L), view<T>(W), vview<T>(alpha), ldlt);
+	if (res >= 0) {
+		st.tag = FaerLltStatus_NonPositivePivot;
+		st.non_positive_pivot.index = (size_t) res;
+	}
+	return st;
+}
+
+// cholesky/ldlt/update.rs:417-434: the indices are sorted in place, then checked
+template <typename T, typename I> void ldlt_delete_api(FaerMatMut LD, FaerSliceMut indices)
+{
+	const size_t n = LD.nrows, r = indices.len;
+	FH_CHECK(LD.ncols == n, "delete_rows_and_cols: LD must be square");
+	if (r == 0)
+		return;
+	FH_CHECK(indices.ptr != nullptr && !is_device_ptr(indices.ptr), "delete_rows_and_cols: the index slice must be host memory");
+	I *ip = static_cast<I *>(indices.ptr);
+	std::sort(ip, ip + r);
+	std::vector<idx_t> idx(r);
+	for (size_t k = 0; k < r; ++k) {
+		FH_CHECK(k == 0 || ip[k] > ip[k - 1], "delete_rows_and_cols: an index is listed twice");
+		idx[k] = (idx_t) ip[k];
+	}
+	FH_CHECK((size_t) ip[r - 1] < n, "delete_rows_and_cols: an index is out of bounds");
+	ctx().ensure_device();
+	ldlt_delete_rows_and_cols<T>(view<T>(LD), idx.data(), (idx_t) r);
 }
 
 template <typename T> FaerEvdStatus self_adjoint_evd_api(FaerMatRef A, FaerMatMut U, FaerVecMut S, FaerSelfAdjointEvdParams params)
@@ -1719,6 +1759,34 @@ void faer_hip_bidiag_in_place_f64(FaerMatMut A, FaerMatMut Hl, FaerMatMut Hr) { 
 void faer_hip_bidiag_in_place_f32(FaerMatMut A, FaerMatMut Hl, FaerMatMut Hr) { bidiag_api<float>(A, Hl, Hr); }
 void faer_hip_hessenberg_in_place_f64(FaerMatMut A, FaerMatMut householder) { hessenberg_api<double>(A, householder); }
 void faer_hip_hessenberg_in_place_f32(FaerMatMut A, FaerMatMut householder) { hessenberg_api<float>(A, householder); }
+
+#define X(suf, T)                                                                                                      \
+	FaerLltStatus faer_hip_llt_rank_r_update_clobber_##suf(FaerMatMut L, FaerMatMut W, FaerVecMut alpha)           \
+	{                                                                                                              \
+		return chol_update_api<T>(L, W, alpha, false);                                                         \
+	}                                                                                                              \
+	void faer_hip_ldlt_rank_r_update_clobber_##suf(FaerMatMut LD, FaerMatMut W, FaerVecMut alpha) { (void) chol_update_api<T>(LD, W, alpha, true); } \
+	void faer_hip_ldlt_delete_rows_and_cols_clobber_u32_##suf(FaerMatMut LD, FaerSliceMut indices, FaerPar par, FaerMemAlloc mem) \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) mem;                                                                                            \
+		ldlt_delete_api<T, uint32_t>(LD, indices);                                                             \
+	}                                                                                                              \
+	void faer_hip_ldlt_delete_rows_and_cols_clobber_u64_##suf(FaerMatMut LD, FaerSliceMut indices, FaerPar par, FaerMemAlloc mem) \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) mem;                                                                                            \
+		ldlt_delete_api<T, uint64_t>(LD, indices);                                                             \
+	}                                                                                                              \
+	FaerLayout faer_hip_ldlt_delete_rows_and_cols_clobber_scratch_##suf(size_t dim, size_t n_removed)              \
+	{                                                                                                              \
+		return layout((dim * n_removed + n_removed) * sizeof(T), 64); /* ldlt/update.rs:402-408 */              \
+	}
+FH_FOR_DTYPES(X)
+#undef X
+void faer_hip_debug_chol_update_last(long out[4]) { chol_update_last(out); }
+void faer_hip_debug_chol_update_diag_only(int on) { chol_update_debug_diag_only(on); }
+void faer_hip_chol_update_shape(int dtype, size_t out[2]) { chol_update_shape(dtype == (int) FaerHipDType_F64 ? 8 : 4, out); }
 
 int faer_hip_debug_lu_leaf_width(size_t nrows, FaerHipDType dtype, int resident_workgroups)
 {

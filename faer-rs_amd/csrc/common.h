@@ -535,6 +535,16 @@ template <typename T>
 int gevd_dev(Arena &arena, MatV<const T> A, MatV<const T> B, MatV<T> UL, MatV<T> UR, T *alpha_re, T *alpha_im, T *beta, idx_t bs, idx_t qr_blocking_threshold,
 	     size_t (*shift_count)(size_t, size_t));
 
+// cholesky/llt/update.rs:360 and cholesky/ldlt/update.rs:376 rank_r_update_clobber (chol_update.hip): the factor in the lower triangle
+// of L (n x n) becomes that of A + W diag(alpha) W^T; W (n x r) and alpha (r x 1) are clobbered.  Each operand is host or device
+// memory on its own; all device memory of the call is one arena.  Returns -1, or the column of the non positive pivot (LLT).
+template <typename T> long chol_rank_update(MatV<T> L, MatV<T> W, MatV<T> alpha, bool ldlt);
+// cholesky/ldlt/update.rs:417 delete_rows_and_cols_clobber: idx holds r >= 1 strictly increasing indices below n (host memory)
+template <typename T> void ldlt_delete_rows_and_cols(MatV<T> LD, const idx_t *idx, idx_t r);
+void chol_update_last(long out[4]); // {column blocks, tail launches, chunks of W per block, host synchronisations inside the block loop} of the last call
+void chol_update_shape(int elem_bytes, size_t out[2]); // {NB, RC}
+void chol_update_debug_diag_only(int on); // measurement aid: 1 = only the diagonal kernels run (the chain of the call; the result is wrong)
+
 // small utility kernels (util.hip)
 template <typename T> void fill_dev(MatV<T> A, DstKind kind, T value);
 template <typename T> void copy_dev(MatV<T> dst, MatV<const T> src);

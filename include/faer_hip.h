@@ -1050,6 +1050,39 @@ FAER_HIP_API void faer_hip_bidiag_in_place_f32(FaerMatMut A, FaerMatMut H_left, 
 FAER_HIP_API void faer_hip_hessenberg_in_place_f64(FaerMatMut A, FaerMatMut householder);
 FAER_HIP_API void faer_hip_hessenberg_in_place_f32(FaerMatMut A, FaerMatMut householder);
 
+/* ------------------------------------------------------------------------------------------------
+ * Modifying an existing Cholesky factorization (faer/src/linalg/cholesky/llt/update.rs:360 rank_r_update_clobber,
+ * cholesky/ldlt/update.rs:376 rank_r_update_clobber and :417 delete_rows_and_cols_clobber; the FFI of the reference does not
+ * export them, so these entry points are extensions with the Rust functions' argument meaning).  Real scalars.
+ *   rank_r_update_clobber: L (n x n, the factor of A in its lower triangle; for LDLT unit lower L with D on the diagonal), W (n x r),
+ *     alpha (r entries).  On return the lower triangle of L holds the factor of A + W diag(alpha) W^T; a negative alpha downdates.
+ *     W and alpha are clobbered (contents unspecified).  The LLT returns NonPositivePivot{index} with the reference's index when a
+ *     new pivot is not positive (a NaN passes, as in the reference); L, W and alpha are unspecified then.
+ *   delete_rows_and_cols_clobber: `indices` (host memory, u32 or u64, sorted in place) names the rows and columns to remove.  On
+ *     return the leading (n - r)^2 block of LD holds the factors of A without them; the trailing r rows are unspecified.
+ *     `mem` is ignored; the _scratch query returns the reference's figure (dim * n_removed + n_removed scalars).
+ * L / LD, W and alpha may each be host or device memory with arbitrary element strides.  Only the lower triangle of a device L is read
+ * or written, and no byte outside a view is written.  n == 0, r == 0 and an empty index list return at once without touching the device.
+ * The call runs on the caller's stream and takes all its device memory from one arena (csrc/chol_update.hip). */
+FAER_HIP_API FaerLltStatus faer_hip_llt_rank_r_update_clobber_f64(FaerMatMut L, FaerMatMut W, FaerVecMut alpha);
+FAER_HIP_API FaerLltStatus faer_hip_llt_rank_r_update_clobber_f32(FaerMatMut L, FaerMatMut W, FaerVecMut alpha);
+FAER_HIP_API void faer_hip_ldlt_rank_r_update_clobber_f64(FaerMatMut LD, FaerMatMut W, FaerVecMut alpha);
+FAER_HIP_API void faer_hip_ldlt_rank_r_update_clobber_f32(FaerMatMut LD, FaerMatMut W, FaerVecMut alpha);
+FAER_HIP_API void faer_hip_ldlt_delete_rows_and_cols_clobber_u32_f64(FaerMatMut LD, FaerSliceMut indices, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API void faer_hip_ldlt_delete_rows_and_cols_clobber_u64_f64(FaerMatMut LD, FaerSliceMut indices, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API void faer_hip_ldlt_delete_rows_and_cols_clobber_u32_f32(FaerMatMut LD, FaerSliceMut indices, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API void faer_hip_ldlt_delete_rows_and_cols_clobber_u64_f32(FaerMatMut LD, FaerSliceMut indices, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout faer_hip_ldlt_delete_rows_and_cols_clobber_scratch_f64(size_t dim, size_t n_removed);
+FAER_HIP_API FaerLayout faer_hip_ldlt_delete_rows_and_cols_clobber_scratch_f32(size_t dim, size_t n_removed);
+/* tests: the calling thread's last call of the family -- out = {column blocks, tail launches, chunks of W per block, host
+ * synchronisations inside the block loop (0)} */
+FAER_HIP_API void faer_hip_debug_chol_update_last(long out[4]);
+/* measurement aid (tools/bench_chol_update.py): 1 = only the diagonal kernels of the family run -- the serial chain of a call; the
+ * factor it leaves is wrong.  Process wide, 0 by default. */
+FAER_HIP_API void faer_hip_debug_chol_update_diag_only(int on);
+/* out = {NB: columns per block, RC: columns of W per chunk}; dtype: a FaerHipDType code.  Needs no device. */
+FAER_HIP_API void faer_hip_chol_update_shape(int dtype, size_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif
