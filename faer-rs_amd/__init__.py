@@ -234,10 +234,10 @@ class Comm(C.Structure):
 
 
 ACCUM_REPLACE, ACCUM_ADD = 0, 1
-CONJ_NO = 0
+CONJ_NO, CONJ_YES = 0, 1
 BLOCK = {"rect": 0, "lower": 1, "upper": 2, "strict_lower": 3, "strict_upper": 4, "unit_lower": 5, "unit_upper": 6}
 DST_FULL, DST_LOWER, DST_UPPER = 0, 1, 2
-DTYPE_F32, DTYPE_F64 = 0, 1
+DTYPE_F32, DTYPE_F64, DTYPE_C32, DTYPE_C64 = 0, 1, 2, 3
 PAR_SEQ = Par(0, 1)
 
 
@@ -311,7 +311,25 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+class C32(C.Structure):
+    """faer's c32: repr(C) {re, im}; built from any Python / numpy scalar"""
+    _fields_ = [("re", C.c_float), ("im", C.c_float)]
+
+    def __init__(self, z=0):
+        z = complex(z)
+        super().__init__(z.real, z.imag)
+
+
+class C64(C.Structure):
+    _fields_ = [("re", C.c_double), ("im", C.c_double)]
+
+    def __init__(self, z=0):
+        z = complex(z)
+        super().__init__(z.real, z.imag)
+
+
 def _dtype_suffix(x):
+    """(suffix of the entry points, ctypes constructor of one scalar, bytes per element); complex scalars exist at level 3 only"""
     if _is_torch(x):
         import torch
 
@@ -319,12 +337,20 @@ def _dtype_suffix(x):
             return "f64", C.c_double, 8
         if x.dtype == torch.float32:
             return "f32", C.c_float, 4
+        if x.dtype == torch.complex128:
+            return "c64", C64, 16
+        if x.dtype == torch.complex64:
+            return "c32", C32, 8
     else:
         if x.dtype == np.float64:
             return "f64", C.c_double, 8
         if x.dtype == np.float32:
             return "f32", C.c_float, 4
-    raise TypeError(f"faer_rs_amd supports f32/f64 only, got {x.dtype}")
+        if x.dtype == np.complex128:
+            return "c64", C64, 16
+        if x.dtype == np.complex64:
+            return "c32", C32, 8
+    raise TypeError(f"faer_rs_amd supports f32 / f64 (and c32 / c64 in matmul, matmul_triangular, gemm and the triangular solves), got {x.dtype}")
 
 
 def _mat(x, cls=MatRef):
@@ -365,8 +391,9 @@ def matmul_triangular(c, c_block, accum, a, a_block, b, b_block, alpha=1.0, par=
     return c
 
 
-def gemm(dst, dst_kind, accum, lhs, rhs, alpha=1.0, row_idx=None, col_idx=None, diag=None):
-    """inner boundary: the private_gemm_x86::gemm call of faer (include/faer_hip.h section 1)."""
+def gemm(dst, dst_kind, accum, lhs, rhs, alpha=1.0, row_idx=None, col_idx=None, diag=None, conj_lhs=False, conj_rhs=False):
+    """inner boundary: the private_gemm_x86::gemm call of faer (include/faer_hip.h section 1).  conj_lhs / conj_rhs conjugate a
+    complex operand (the identity for real ones); complex products take no row_idx / col_idx / diag."""
     suf, ct, _ = _dtype_suffix(dst)
     al = ct(alpha)
     m, k = lhs.shape
@@ -392,11 +419,11 @@ def gemm(dst, dst_kind, accum, lhs, rhs, alpha=1.0, row_idx=None, col_idx=None, 
     if diag is not None:
         dg = C.c_void_p(diag.data_ptr() if _is_torch(diag) else diag.ctypes.data)
         dgs = diag.stride(0) if _is_torch(diag) else diag.strides[0] // diag.itemsize
-    lib().faer_hip_gemm(C.c_int(DTYPE_F64 if suf == "f64" else DTYPE_F32), C.c_int(itype), C.c_size_t(m), C.c_size_t(n),
+    lib().faer_hip_gemm(C.c_int({"f32": DTYPE_F32, "f64": DTYPE_F64, "c32": DTYPE_C32, "c64": DTYPE_C64}[suf]), C.c_int(itype), C.c_size_t(m), C.c_size_t(n),
                         C.c_size_t(k), C.c_void_p(d.ptr), C.c_ssize_t(d.row_stride), C.c_ssize_t(d.col_stride), ri, ci,
                         C.c_int(dst_kind), C.c_int(accum), C.c_void_p(a.ptr), C.c_ssize_t(a.row_stride),
-                        C.c_ssize_t(a.col_stride), C.c_bool(False), dg, C.c_ssize_t(dgs), C.c_void_p(b.ptr),
-                        C.c_ssize_t(b.row_stride), C.c_ssize_t(b.col_stride), C.c_bool(False), C.byref(al), C.c_size_t(0))
+                        C.c_ssize_t(a.col_stride), C.c_bool(bool(conj_lhs)), dg, C.c_ssize_t(dgs), C.c_void_p(b.ptr),
+                        C.c_ssize_t(b.row_stride), C.c_ssize_t(b.col_stride), C.c_bool(bool(conj_rhs)), C.byref(al), C.c_size_t(0))
     return dst
 
 
@@ -423,26 +450,27 @@ def debug_gemm_plan(**problem):
     return why.value.decode() if rc == 1 else None
 
 
-def _trsm(name, t, rhs, par):
+def _trsm(name, t, rhs, par, conj=False):
+    """rhs <- op(t)^-1 rhs; conj: op is the conjugate (complex scalars; the real entry points ignore it)"""
     suf, _, _ = _dtype_suffix(rhs)
-    getattr(lib(), f"libfaer_v0_23_{name}_{suf}")(_mat(t), C.c_int(CONJ_NO), _mat(rhs, MatMut), par)
+    getattr(lib(), f"libfaer_v0_23_{name}_{suf}")(_mat(t), C.c_int(CONJ_YES if conj else CONJ_NO), _mat(rhs, MatMut), par)
     return rhs
 
 
-def solve_lower_triangular_in_place(l, rhs, par=PAR_SEQ):
-    return _trsm("solve_triangular_lower_in_place", l, rhs, par)
+def solve_lower_triangular_in_place(l, rhs, par=PAR_SEQ, conj=False):
+    return _trsm("solve_triangular_lower_in_place", l, rhs, par, conj)
 
 
-def solve_upper_triangular_in_place(u, rhs, par=PAR_SEQ):
-    return _trsm("solve_triangular_upper_in_place", u, rhs, par)
+def solve_upper_triangular_in_place(u, rhs, par=PAR_SEQ, conj=False):
+    return _trsm("solve_triangular_upper_in_place", u, rhs, par, conj)
 
 
-def solve_unit_lower_triangular_in_place(l, rhs, par=PAR_SEQ):
-    return _trsm("solve_unit_triangular_lower_in_place", l, rhs, par)
+def solve_unit_lower_triangular_in_place(l, rhs, par=PAR_SEQ, conj=False):
+    return _trsm("solve_unit_triangular_lower_in_place", l, rhs, par, conj)
 
 
-def solve_unit_upper_triangular_in_place(u, rhs, par=PAR_SEQ):
-    return _trsm("solve_unit_triangular_upper_in_place", u, rhs, par)
+def solve_unit_upper_triangular_in_place(u, rhs, par=PAR_SEQ, conj=False):
+    return _trsm("solve_unit_triangular_upper_in_place", u, rhs, par, conj)
 
 
 def llt_factor_in_place(a, regularization=(0.0, 0.0), par=PAR_SEQ):

@@ -44,12 +44,15 @@ void matmul_triangular_api(FaerMatMut C, FaerBlock cb, FaerAccum accum, FaerMatR
 	matmul_triangular_dev<T>(c.dev, (int) cb, add, a.dev, (int) ab, b.dev, (int) bb, *static_cast<const T *>(alpha));
 }
 
-template <typename T> void trsm_api(FaerMatRef Tm, FaerMatMut rhs, bool upper, bool unit)
+// conj: complex scalars only (conjugation is the identity for real ones)
+template <typename T> void trsm_api(FaerMatRef Tm, FaerMatMut rhs, bool upper, bool unit, bool conj = false)
 {
 	FH_CHECK(Tm.nrows == Tm.ncols && rhs.nrows == Tm.ncols, "triangular solve: dimension mismatch");
 	Staged<const T> t(view<T>(Tm), true, false);
 	Staged<T> x(view<T>(rhs), true, true);
-	if (upper)
+	if constexpr (is_cx<T>::value)
+		ctrsm_dev(t.dev, upper, unit, conj, x.dev);
+	else if (upper)
 		trsm_upper_dev<T>(t.dev, unit, x.dev);
 	else
 		trsm_lower_dev<T>(t.dev, unit, x.dev);
@@ -852,10 +855,11 @@ void faer_hip_gemm(FaerHipDType dtype, FaerHipIType itype, size_t m, size_t n, s
 		   const void *lhs, ptrdiff_t lhs_rs, ptrdiff_t lhs_cs, bool conj_lhs, const void *diag, ptrdiff_t diag_stride,
 		   const void *rhs, ptrdiff_t rhs_rs, ptrdiff_t rhs_cs, bool conj_rhs, const void *alpha, size_t n_threads)
 {
-	(void) conj_lhs; // conjugation is the identity for real scalars
-	(void) conj_rhs;
 	(void) n_threads;
-	FH_CHECK(dtype == FaerHipDType_F32 || dtype == FaerHipDType_F64, "faer_hip_gemm: only f32/f64 are supported");
+	const bool cx = dtype == FaerHipDType_C32 || dtype == FaerHipDType_C64;
+	FH_CHECK(cx || dtype == FaerHipDType_F32 || dtype == FaerHipDType_F64, "faer_hip_gemm: unknown dtype");
+	FH_CHECK(!cx || (!row_idx && !col_idx && !diag),
+		 "faer_hip_gemm: row_idx / col_idx / diag are not implemented for complex scalars (c32 / c64)");
 	FH_CHECK(alpha != nullptr, "faer_hip_gemm: alpha is NULL");
 	if (m == 0 || n == 0)
 		return;
@@ -902,16 +906,63 @@ void faer_hip_gemm(FaerHipDType dtype, FaerHipIType itype, size_t m, size_t n, s
 		ex.idx64 = isz == 8;
 		ex.diag = diag ? dg.dev.p : nullptr;
 		ex.diag_stride = dg.dev.rs; // 1 for a staged host vector, the caller's stride for a device one
+		ex.conj_lhs = conj_lhs;	    // (the real kernels never look: conjugation is the identity there)
+		ex.conj_rhs = conj_rhs;
 		MatV<T> Cv{c.dev.p, (idx_t) m, (idx_t) n, c.dev.rs, c.dev.cs};
 		gemm_dev<T>(Cv, (DstKind) dst_kind, add, a.dev, b.dev, *static_cast<const T *>(alpha), &ex);
 	};
 	if (dtype == FaerHipDType_F64)
 		run(double());
-	else
+	else if (dtype == FaerHipDType_F32)
 		run(float());
+	else if (dtype == FaerHipDType_C64)
+		run(c64());
+	else
+		run(c32());
 }
 
 // ---------------------------------------------------------------------------------------- outer boundary
+// complex level 3 (faer-ffi/src/lib.rs:855-937): the same templates on c32 / c64, the triangular solves honour their FaerConj
+#define X(suf)                                                                                                         \
+	void libfaer_v0_23_matmul_##suf(FaerMatMut C, FaerAccum accum, FaerMatRef A, FaerMatRef B, const void *alpha,    \
+					FaerPar par)                                                                        \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		matmul_api<suf>(C, accum, A, B, alpha);                                                                \
+	}                                                                                                              \
+	void libfaer_v0_23_matmul_triangular_##suf(FaerMatMut C, FaerBlock C_block, FaerAccum accum, FaerMatRef A,      \
+						   FaerBlock A_block, FaerMatRef B, FaerBlock B_block, const void *alpha,    \
+						   FaerPar par)                                                             \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		matmul_triangular_api<suf>(C, C_block, accum, A, A_block, B, B_block, alpha);                           \
+	}                                                                                                              \
+	void libfaer_v0_23_solve_triangular_lower_in_place_##suf(FaerMatRef L, FaerConj cj, FaerMatMut rhs, FaerPar par) \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		trsm_api<suf>(L, rhs, false, false, cj == FaerConj_Yes);                                               \
+	}                                                                                                              \
+	void libfaer_v0_23_solve_triangular_upper_in_place_##suf(FaerMatRef U, FaerConj cj, FaerMatMut rhs, FaerPar par) \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		trsm_api<suf>(U, rhs, true, false, cj == FaerConj_Yes);                                                \
+	}                                                                                                              \
+	void libfaer_v0_23_solve_unit_triangular_lower_in_place_##suf(FaerMatRef L, FaerConj cj, FaerMatMut rhs,        \
+								      FaerPar par)                                          \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		trsm_api<suf>(L, rhs, false, true, cj == FaerConj_Yes);                                                \
+	}                                                                                                              \
+	void libfaer_v0_23_solve_unit_triangular_upper_in_place_##suf(FaerMatRef U, FaerConj cj, FaerMatMut rhs,        \
+								      FaerPar par)                                          \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		trsm_api<suf>(U, rhs, true, true, cj == FaerConj_Yes);                                                 \
+	}
+X(c64)
+X(c32)
+#undef X
+
 #define FH_FOR_DTYPES(X) X(f64, double) X(f32, float)
 
 #define X(suf, T)                                                                                                      \

@@ -45,6 +45,16 @@ typedef long idx_t;
 static __device__ __forceinline__ double fh_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 static __device__ __forceinline__ float fh_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
+// complex scalars of the boundary: faer's c32 / c64 are repr(C) {re, im}, interleaved (strides stay in complex elements).
+// Only level 3 knows them (cgemm.hip, ctrsm.hip); everything else in the tree is instantiated for float / double.
+template <typename R> struct Cx {
+	R re, im;
+};
+typedef Cx<float> c32;
+typedef Cx<double> c64;
+template <typename T> struct is_cx : std::false_type {};
+template <typename R> struct is_cx<Cx<R>> : std::true_type {};
+
 template <typename T> struct MatV {
 	T *p;
 	idx_t nrows, ncols, rs, cs;
@@ -339,6 +349,8 @@ template <typename T> struct GemmExtra {
 	// short-wide / tall-narrow FULL output with a deep K (the V^H A product of a QR block application, 128 x n with K = rows): 128 x 128
 	// tiles with more K slices instead of the 64 x 64 tiles the tile-count rule picks (square QR N = 8192: -3 %, tools/gpu_qr_square_gemm_ab.py)
 	bool prefer_big_tiles = false;
+	// complex scalars only (cgemm.hip): op(lhs) / op(rhs) is the conjugate (the real kernels never look at these)
+	bool conj_lhs = false, conj_rhs = false;
 };
 
 // Ctx::gemm_variant (faer_hip_set_gemm_variant): the integers are public, tools and tests pass them through
@@ -442,9 +454,19 @@ double mfma_peak_tflops(bool f64, int iters);
 template <typename T>
 void matmul_triangular_dev(MatV<T> C, int c_s, bool add, MatV<const T> A, int a_s, MatV<const T> B, int b_s, T alpha);
 
+// complex scalars (cgemm.hip): the same two drivers on the complex MFMA kernel.  GemmExtra::conj_lhs / conj_rhs are honoured, all seven
+// FaerBlock kinds and the three DstKinds are masked loads / stores of that one kernel; row_idx / col_idx / diag are refused.  No workspace.
+template <> void gemm_dev<c32>(MatV<c32> C, DstKind kind, bool add, MatV<const c32> A, MatV<const c32> B, c32 alpha, const GemmExtra<c32> *extra);
+template <> void gemm_dev<c64>(MatV<c64> C, DstKind kind, bool add, MatV<const c64> A, MatV<const c64> B, c64 alpha, const GemmExtra<c64> *extra);
+template <> void matmul_triangular_dev<c32>(MatV<c32> C, int c_s, bool add, MatV<const c32> A, int a_s, MatV<const c32> B, int b_s, c32 alpha);
+template <> void matmul_triangular_dev<c64>(MatV<c64> C, int c_s, bool add, MatV<const c64> A, int a_s, MatV<const c64> B, int b_s, c64 alpha);
+
 // X <- op(T)^-1 X, T lower triangular n x n, X n x k (trsm.hip); upper handled by reversal
 template <typename T> void trsm_lower_dev(MatV<const T> L, bool unit, MatV<T> X);
 template <typename T> void trsm_upper_dev(MatV<const T> U, bool unit, MatV<T> X);
+// complex scalars (ctrsm.hip): X <- op(T)^-1 X with op the identity or the conjugate; blocked substitution, the updates on gemm_dev<Cx<R>>
+template <typename R> void ctrsm_dev(MatV<const Cx<R>> T, bool upper, bool unit, bool conj, MatV<Cx<R>> X);
+idx_t ctrsm_leaf_rows(); // rows of the diagonal blocks the substitution kernel solves
 // same as trsm_lower_dev with the packed images (trsm_pack.h) of L's 128 x 128 diagonal blocks already in W
 template <typename T> void trsm_lower_pre_dev(MatV<const T> L, MatV<T> X, const T *W);
 template <typename T> void trsm_pack_dev(MatV<const T> L, bool unit, T *W);

@@ -210,7 +210,9 @@ typedef enum FaerHipDstKind { FaerHipDstKind_Full = 0, FaerHipDstKind_Lower = 1,
 
 /* dst[row_idx[i], col_idx[j]] (or dst[i,j] when the index arrays are NULL), restricted to the
  * Full / Lower (i>=j) / Upper (i<=j) part, <- [dst +] alpha * lhs * diag(diag) * rhs.
- * Accum_Replace never reads dst.  F32/F64 only (C32/C64 abort: out of the north-star scope).
+ * Accum_Replace never reads dst.  F32 / F64 and C32 / C64 (interleaved {re, im}; strides in complex elements, alpha points at
+ * one {re, im}).  conj_lhs / conj_rhs conjugate the operand (the identity for real scalars).  For C32 / C64 row_idx, col_idx and
+ * diag must be NULL: the call aborts with a message that says so.
  * n_threads is accepted for signature compatibility and ignored.  Thread safe. */
 FAER_HIP_API void faer_hip_gemm(FaerHipDType dtype, FaerHipIType itype, size_t m, size_t n, size_t k,
                                 void *dst, ptrdiff_t dst_rs, ptrdiff_t dst_cs,
@@ -222,7 +224,8 @@ FAER_HIP_API void faer_hip_gemm(FaerHipDType dtype, FaerHipIType itype, size_t m
                                 const void *alpha, size_t n_threads);
 
 /* ---------------------------------------------------------------------------------------------
- * 2. OUTER boundary -- faer-ffi symbol-compatible entry points (f32 / f64).
+ * 2. OUTER boundary -- faer-ffi symbol-compatible entry points (f32 / f64; level 3 -- matmul, matmul_triangular and the
+ *    four triangular solves -- also c32 / c64, where the FaerConj argument of the solves is honoured).
  *    Each comment cites the Rust function in faer-ffi/src/lib.rs it replaces.
  * --------------------------------------------------------------------------------------------- */
 /* A client that includes the reference's own faer-ffi/faer.h for these prototypes (tests/cabi_client/) defines
@@ -232,18 +235,30 @@ FAER_HIP_API void faer_hip_gemm(FaerHipDType dtype, FaerHipIType itype, size_t m
 /* lib.rs:855-871  la::matmul::matmul */
 FAER_HIP_API void libfaer_v0_23_matmul_f64(FaerMatMut C, FaerAccum accum, FaerMatRef A, FaerMatRef B, const void *alpha, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_matmul_f32(FaerMatMut C, FaerAccum accum, FaerMatRef A, FaerMatRef B, const void *alpha, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_matmul_c64(FaerMatMut C, FaerAccum accum, FaerMatRef A, FaerMatRef B, const void *alpha, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_matmul_c32(FaerMatMut C, FaerAccum accum, FaerMatRef A, FaerMatRef B, const void *alpha, FaerPar par);
 /* lib.rs:872-895  la::matmul::triangular::matmul */
 FAER_HIP_API void libfaer_v0_23_matmul_triangular_f64(FaerMatMut C, FaerBlock C_block, FaerAccum accum, FaerMatRef A, FaerBlock A_block, FaerMatRef B, FaerBlock B_block, const void *alpha, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_matmul_triangular_f32(FaerMatMut C, FaerBlock C_block, FaerAccum accum, FaerMatRef A, FaerBlock A_block, FaerMatRef B, FaerBlock B_block, const void *alpha, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_matmul_triangular_c64(FaerMatMut C, FaerBlock C_block, FaerAccum accum, FaerMatRef A, FaerBlock A_block, FaerMatRef B, FaerBlock B_block, const void *alpha, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_matmul_triangular_c32(FaerMatMut C, FaerBlock C_block, FaerAccum accum, FaerMatRef A, FaerBlock A_block, FaerMatRef B, FaerBlock B_block, const void *alpha, FaerPar par);
 /* lib.rs:896-937  la::triangular_solve::solve_{,unit_}{lower,upper}_triangular_in_place_with_conj */
 FAER_HIP_API void libfaer_v0_23_solve_triangular_lower_in_place_f64(FaerMatRef L, FaerConj L_conj, FaerMatMut rhs, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_solve_triangular_lower_in_place_f32(FaerMatRef L, FaerConj L_conj, FaerMatMut rhs, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_solve_triangular_lower_in_place_c64(FaerMatRef L, FaerConj L_conj, FaerMatMut rhs, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_solve_triangular_lower_in_place_c32(FaerMatRef L, FaerConj L_conj, FaerMatMut rhs, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_solve_triangular_upper_in_place_f64(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_solve_triangular_upper_in_place_f32(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_solve_triangular_upper_in_place_c64(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_solve_triangular_upper_in_place_c32(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_lower_in_place_f64(FaerMatRef L, FaerConj L_conj, FaerMatMut rhs, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_lower_in_place_f32(FaerMatRef L, FaerConj L_conj, FaerMatMut rhs, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_lower_in_place_c64(FaerMatRef L, FaerConj L_conj, FaerMatMut rhs, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_lower_in_place_c32(FaerMatRef L, FaerConj L_conj, FaerMatMut rhs, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_upper_in_place_f64(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_upper_in_place_f32(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_upper_in_place_c64(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_upper_in_place_c32(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
 
 /* lib.rs:650-655 (cparams! getter)  Auto<T> for LltParams: {64, 128} (cholesky/ldlt/factor.rs:705-714) */
 FAER_HIP_API FaerLltParams libfaer_v0_23_LltParams_f64(void);
