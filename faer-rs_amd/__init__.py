@@ -287,6 +287,13 @@ def lib():
             for name in ("piv_llt_factor_in_place_scratch", "piv_llt_solve_in_place_scratch", "piv_llt_reconstruct_scratch",
                          "piv_llt_inverse_scratch"):
                 getattr(L, f"libfaer_v0_23_{name}_{it}_{suf}").restype = Layout
+    for suf in ("c64", "c32"):  # complex partial-pivot LU
+        getattr(L, f"libfaer_v0_23_PartialPivLuParams_{suf}").restype = PartialPivLuParams
+        for it in ("u32", "u64"):
+            getattr(L, f"libfaer_v0_23_partial_piv_lu_factor_in_place_{it}_{suf}").restype = PartialPivLuStatus
+            for name in ("partial_piv_lu_factor_in_place_scratch", "partial_piv_lu_solve_in_place_scratch",
+                         "partial_piv_lu_solve_transpose_in_place_scratch"):
+                getattr(L, f"libfaer_v0_23_{name}_{it}_{suf}").restype = Layout
     L.libfaer_v0_23_get_global_par.restype = Par
     L.faer_hip_version.restype = C.c_char_p
     L.faer_hip_device_count.restype = C.c_int
@@ -329,7 +336,8 @@ class C64(C.Structure):
 
 
 def _dtype_suffix(x):
-    """(suffix of the entry points, ctypes constructor of one scalar, bytes per element); complex scalars exist at level 3 only"""
+    """(suffix of the entry points, ctypes constructor of one scalar, bytes per element); complex scalars exist at level 3 and in the
+    partial-pivot LU only"""
     if _is_torch(x):
         import torch
 
@@ -350,7 +358,8 @@ def _dtype_suffix(x):
             return "c64", C64, 16
         if x.dtype == np.complex64:
             return "c32", C32, 8
-    raise TypeError(f"faer_rs_amd supports f32 / f64 (and c32 / c64 in matmul, matmul_triangular, gemm and the triangular solves), got {x.dtype}")
+    raise TypeError(f"faer_rs_amd supports f32 / f64 (and c32 / c64 in matmul, matmul_triangular, gemm, the triangular solves and the "
+                    f"partial-pivot LU with its solves), got {x.dtype}")
 
 
 def _mat(x, cls=MatRef):
@@ -1365,6 +1374,22 @@ def debug_piv_llt_last():
     return tuple(int(v) for v in out)
 
 
+def debug_clu_shape(dtype):
+    """(W, leaf_rows) of the complex partial-pivot LU: columns per panel and the row count of the tallest panel its LDS-resident leaf
+    takes; dtype complex64 or complex128.  Needs no GPU."""
+    out = (C.c_size_t * 2)()
+    lib().faer_hip_debug_clu_shape(C.c_int(DTYPE_C64 if np.dtype(dtype) == np.complex128 else DTYPE_C32), out)
+    return int(out[0]), int(out[1])
+
+
+def debug_clu_last():
+    """{panels on the LDS leaf, panels on the column-step kernels, column-step launches, interchange launches} of this thread's last
+    complex partial_piv_lu_factor_in_place"""
+    out = (C.c_size_t * 4)()
+    lib().faer_hip_debug_clu_last(out)
+    return dict(zip(("leaf_panels", "step_panels", "step_launches", "swap_launches"), (int(v) for v in out)))
+
+
 def debug_scratch_fill(byte=-1):
     """tests: from now on every device scratch buffer the library hands to itself is first filled, over its whole pool size, with
     `byte` (0 .. 255); -1 switches the fill off again (the default).  Process wide; resets debug_scratch_fill_stats."""
@@ -1393,14 +1418,15 @@ def _copy_f(a):
     return np.array(a, order="F", copy=True)
 
 
-def partial_piv_lu_solve_in_place(lu, perm_fwd, perm_bwd, rhs, transpose=False, par=PAR_SEQ):
-    """lu/partial_pivoting/solve.rs:20-80: rhs <- A^-1 rhs (or A^-T rhs); `lu` holds L (unit lower) and U packed"""
+def partial_piv_lu_solve_in_place(lu, perm_fwd, perm_bwd, rhs, transpose=False, par=PAR_SEQ, conj=False):
+    """lu/partial_pivoting/solve.rs:20-80: rhs <- op(A)^-1 rhs (or op(A)^-T rhs); `lu` holds L (unit lower) and U packed.
+    conj: op is the conjugate (complex scalars; the real entry points ignore it)"""
     suf, _, _ = _dtype_suffix(lu)
     it = "u64" if np.dtype(perm_fwd.dtype) == np.uint64 else "u32"
     name = "partial_piv_lu_solve_transpose_in_place" if transpose else "partial_piv_lu_solve_in_place"
     n = lu.shape[0]
     getattr(lib(), f"libfaer_v0_23_{name}_{it}_{suf}")(
-        _mat(lu), _mat(lu), C.c_int(0), SliceRef(perm_fwd.ctypes.data, n), SliceRef(perm_bwd.ctypes.data, n), _mat(rhs, MatMut), par,
+        _mat(lu), _mat(lu), C.c_int(CONJ_YES if conj else CONJ_NO), SliceRef(perm_fwd.ctypes.data, n), SliceRef(perm_bwd.ctypes.data, n), _mat(rhs, MatMut), par,
         MemAlloc(None, 0))
     return rhs
 

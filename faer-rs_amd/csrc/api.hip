@@ -203,9 +203,9 @@ template <typename T> void apply_hh_api(FaerMatRef V, FaerMatRef H, FaerMatMut r
 	apply_householder_sequence_left_dev<T>(v.dev, h.dev, x.dev, transpose);
 }
 
-// lu/partial_pivoting/solve.rs:20-50 and :52-80
+// lu/partial_pivoting/solve.rs:20-50 and :52-80; conj (complex scalars only): the system is conj(A) X = B / conj(A)^T X = B
 template <typename T, typename I>
-void lu_solve_api(FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, bool transpose)
+void lu_solve_api(FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, bool transpose, bool conj = false)
 {
 	const size_t n = L.nrows;
 	FH_CHECK(L.ncols == n && U.nrows == n && U.ncols == n && rhs.nrows == n, "partial_piv_lu solve: dimension mismatch");
@@ -213,7 +213,17 @@ void lu_solve_api(FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, 
 	DevPerm perm("partial_piv_lu solve", transpose ? pb : pf, (idx_t) n, I{});
 	Staged<const T> l(view<T>(L), true, false), u(view<T>(U), true, false);
 	Staged<T> x(view<T>(rhs), true, true);
-	if (!transpose) {
+	if constexpr (is_cx<T>::value) {
+		if (!transpose) {
+			permute_rows<T>(x.dev, perm);
+			ctrsm_dev(l.dev, false, true, conj, x.dev);
+			ctrsm_dev(u.dev, true, false, conj, x.dev);
+		} else {
+			ctrsm_dev(u.dev.t(), false, false, conj, x.dev);
+			ctrsm_dev(l.dev.t(), true, true, conj, x.dev);
+			permute_rows<T>(x.dev, perm); // the inverse permutation
+		}
+	} else if (!transpose) {
 		permute_rows<T>(x.dev, perm);
 		trsm_lower_dev<T>(l.dev, true, x.dev);
 		trsm_upper_dev<T>(u.dev, false, x.dev);
@@ -962,6 +972,57 @@ void faer_hip_gemm(FaerHipDType dtype, FaerHipIType itype, size_t m, size_t n, s
 X(c64)
 X(c32)
 #undef X
+
+// complex partial-pivot LU (faer-ffi/src/lib.rs:1952-1984 and the solves): the templates of the real family on c32 / c64 (cgetrf.hip);
+// the solves honour A_conj.  The scratch queries are the reference's: indices for the factorization, one copy of rhs for a solve.
+#define X(suf, it, I)                                                                                                  \
+	FaerLayout libfaer_v0_23_partial_piv_lu_factor_in_place_scratch_##it##_##suf(size_t dim, size_t bs, FaerPar par, \
+										      FaerPartialPivLuParams params)        \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) params;                                                                                         \
+		return layout((dim < bs ? dim : bs) * sizeof(I), sizeof(I));                                           \
+	}                                                                                                              \
+	FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_##it##_##suf(                               \
+		FaerMatMut A, FaerSliceMut pf, FaerSliceMut pb, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params) \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) mem;                                                                                            \
+		(void) params;                                                                                         \
+		return lu_api<suf, I>(A, pf, pb);                                                                      \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_##it##_##suf(size_t dim, size_t k, FaerPar par)  \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		return layout(dim * k * sizeof(suf), 64);                                                              \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_##it##_##suf(size_t dim, size_t k, FaerPar par) \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		return layout(dim * k * sizeof(suf), 64);                                                              \
+	}                                                                                                              \
+	void libfaer_v0_23_partial_piv_lu_solve_in_place_##it##_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef pf, \
+								      FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) mem;                                                                                            \
+		lu_solve_api<suf, I>(L, U, pf, pb, rhs, false, cj == FaerConj_Yes);                                    \
+	}                                                                                                              \
+	void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_##it##_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, \
+										FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, \
+										FaerPar par, FaerMemAlloc mem)              \
+	{                                                                                                              \
+		(void) par;                                                                                            \
+		(void) mem;                                                                                            \
+		lu_solve_api<suf, I>(L, U, pf, pb, rhs, true, cj == FaerConj_Yes);                                     \
+	}
+X(c64, u32, uint32_t)
+X(c64, u64, uint64_t)
+X(c32, u32, uint32_t)
+X(c32, u64, uint64_t)
+#undef X
+FaerPartialPivLuParams libfaer_v0_23_PartialPivLuParams_c64(void) { return FaerPartialPivLuParams{16, 64, 128 * 128}; }
+FaerPartialPivLuParams libfaer_v0_23_PartialPivLuParams_c32(void) { return FaerPartialPivLuParams{16, 64, 128 * 128}; }
 
 #define FH_FOR_DTYPES(X) X(f64, double) X(f32, float)
 
@@ -1838,6 +1899,8 @@ FH_FOR_DTYPES(X)
 void faer_hip_debug_chol_update_last(long out[4]) { chol_update_last(out); }
 void faer_hip_debug_chol_update_diag_only(int on) { chol_update_debug_diag_only(on); }
 void faer_hip_chol_update_shape(int dtype, size_t out[2]) { chol_update_shape(dtype == (int) FaerHipDType_F64 ? 8 : 4, out); }
+void faer_hip_debug_clu_shape(int dtype, size_t out[2]) { clu_shape(dtype == (int) FaerHipDType_C64 ? 16 : 8, out); }
+void faer_hip_debug_clu_last(size_t out[4]) { clu_last(out); }
 
 int faer_hip_debug_lu_leaf_width(size_t nrows, FaerHipDType dtype, int resident_workgroups)
 {

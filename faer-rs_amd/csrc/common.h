@@ -46,7 +46,8 @@ static __device__ __forceinline__ double fh_fma(double a, double b, double c) { 
 static __device__ __forceinline__ float fh_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
 // complex scalars of the boundary: faer's c32 / c64 are repr(C) {re, im}, interleaved (strides stay in complex elements).
-// Only level 3 knows them (cgemm.hip, ctrsm.hip); everything else in the tree is instantiated for float / double.
+// Level 3 (cgemm.hip, ctrsm.hip) and the partial-pivot LU (cgetrf.hip) know them; everything else in the tree is instantiated for
+// float / double.
 template <typename R> struct Cx {
 	R re, im;
 };
@@ -484,6 +485,11 @@ template <typename T> long sytrf_lower_dev(MatV<T> A, T reg_delta, T reg_eps, co
 
 // partial pivot LU; perm/perm_inv are HOST arrays of idx_t (m entries)   (getrf.hip)
 template <typename T> long getrf_dev(MatV<T> A, idx_t *perm, idx_t *perm_inv);
+// complex scalars (cgetrf.hip): the reference's recursion on panels of W columns; pivots by abs1 = |re| + |im|.  Never returns < 0.
+template <> long getrf_dev<c32>(MatV<c32> A, idx_t *perm, idx_t *perm_inv);
+template <> long getrf_dev<c64>(MatV<c64> A, idx_t *perm, idx_t *perm_inv);
+void clu_shape(int elem_bytes, size_t out[2]); // {W, rows of the tallest panel the LDS leaf takes}; elem_bytes 8 (c32) or 16 (c64)
+void clu_last(size_t out[4]); // {panels on the LDS leaf, panels on the column-step kernels, column-step launches, interchange launches} of the calling thread's last complex LU
 
 // pieces of the LU driver used by the distributed driver (dist.hip): in-place factorization of an m x w panel
 // (w <= m) with the pivots left on the device (piv_dev[j] = row swapped with row j, relative to the panel), and

@@ -88,5 +88,10 @@ template void gather_rows_dev<float>(MatV<float>, MatV<const float>, const idx_t
 template void copy_dev<double>(MatV<double>, MatV<const double>);
 template void copy_dev<float>(MatV<float>, MatV<const float>);
 template void copy_dev<long>(MatV<long>, MatV<const long>);
+// complex right-hand sides of the LU solves (permute_rows)
+template void gather_rows_dev<c64>(MatV<c64>, MatV<const c64>, const idx_t *);
+template void gather_rows_dev<c32>(MatV<c32>, MatV<const c32>, const idx_t *);
+template void copy_dev<c64>(MatV<c64>, MatV<const c64>);
+template void copy_dev<c32>(MatV<c32>, MatV<const c32>);
 
 } // namespace fh

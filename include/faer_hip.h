@@ -225,7 +225,8 @@ FAER_HIP_API void faer_hip_gemm(FaerHipDType dtype, FaerHipIType itype, size_t m
 
 /* ---------------------------------------------------------------------------------------------
  * 2. OUTER boundary -- faer-ffi symbol-compatible entry points (f32 / f64; level 3 -- matmul, matmul_triangular and the
- *    four triangular solves -- also c32 / c64, where the FaerConj argument of the solves is honoured).
+ *    four triangular solves -- and the partial-pivot LU with its two solves also c32 / c64, where the FaerConj argument of
+ *    the solves is honoured).
  *    Each comment cites the Rust function in faer-ffi/src/lib.rs it replaces.
  * --------------------------------------------------------------------------------------------- */
 /* A client that includes the reference's own faer-ffi/faer.h for these prototypes (tests/cabi_client/) defines
@@ -289,6 +290,17 @@ FAER_HIP_API FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place
 FAER_HIP_API FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_u64_f64(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params);
 FAER_HIP_API FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_u32_f32(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params);
 FAER_HIP_API FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_u64_f32(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params);
+/* the same for c32 / c64 (cgetrf.hip): the pivot of a column is its first entry of largest abs1 = |re| + |im| (factor.rs:35-43) */
+FAER_HIP_API FaerPartialPivLuParams libfaer_v0_23_PartialPivLuParams_c64(void);
+FAER_HIP_API FaerPartialPivLuParams libfaer_v0_23_PartialPivLuParams_c32(void);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_factor_in_place_scratch_u32_c64(size_t dim, size_t block_size, FaerPar par, FaerPartialPivLuParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_factor_in_place_scratch_u64_c64(size_t dim, size_t block_size, FaerPar par, FaerPartialPivLuParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_factor_in_place_scratch_u32_c32(size_t dim, size_t block_size, FaerPar par, FaerPartialPivLuParams params);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_factor_in_place_scratch_u64_c32(size_t dim, size_t block_size, FaerPar par, FaerPartialPivLuParams params);
+FAER_HIP_API FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_u32_c64(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params);
+FAER_HIP_API FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_u64_c64(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params);
+FAER_HIP_API FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_u32_c32(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params);
+FAER_HIP_API FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_u64_c32(FaerMatMut A, FaerSliceMut perm_fwd, FaerSliceMut perm_bwd, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params);
 
 /* lib.rs:667-671  Auto<T> for QrParams: {48*48, 192*256} (qr/no_pivoting/factor.rs:127-136) */
 FAER_HIP_API FaerQrParams libfaer_v0_23_QrParams_f64(void);
@@ -332,6 +344,23 @@ FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_u64_
 FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_in_place_u64_f32(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
 FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_u64_f32(size_t dim, size_t rhs_ncols, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_u64_f32(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+/* the same for c32 / c64, where A_conj is honoured: op(A) X = rhs / op(A)^T X = rhs with op the identity or the conjugate (solve.rs:21-87) */
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_u32_c64(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_in_place_u32_c64(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_u32_c64(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_u32_c64(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_u32_c32(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_in_place_u32_c32(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_u32_c32(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_u32_c32(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_u64_c64(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_in_place_u64_c64(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_u64_c64(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_u64_c64(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_u64_c32(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_in_place_u64_c32(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
+FAER_HIP_API FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_u64_c32(size_t dim, size_t rhs_ncols, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_u64_c32(FaerMatRef L, FaerMatRef U, FaerConj A_conj, FaerSliceRef perm_fwd, FaerSliceRef perm_bwd, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem);
 /* lib.rs:1560-1660  qr::no_pivoting::solve::{solve_in_place, solve_transpose_in_place, solve_lstsq_in_place}_with_conj
  * (qr/no_pivoting/solve.rs:38-175): rhs <- R^-1 Q^H rhs (square or least squares: the solution is the top
  * ncols rows of rhs), resp. rhs <- Q R^-T rhs. */
@@ -1097,6 +1126,14 @@ FAER_HIP_API void faer_hip_debug_chol_update_last(long out[4]);
 FAER_HIP_API void faer_hip_debug_chol_update_diag_only(int on);
 /* out = {NB: columns per block, RC: columns of W per chunk}; dtype: a FaerHipDType code.  Needs no device. */
 FAER_HIP_API void faer_hip_chol_update_shape(int dtype, size_t out[2]);
+
+/* Complex partial-pivot LU (cgetrf.hip).
+ * out = {W: columns per panel, the row count of the tallest panel the LDS-resident leaf takes}; dtype: FaerHipDType_C32 / _C64.
+ * Needs no device. */
+FAER_HIP_API void faer_hip_debug_clu_shape(int dtype, size_t out[2]);
+/* tests: the calling thread's last complex partial_piv_lu_factor_in_place -- out = {panels on the LDS leaf, panels on the
+ * column-step kernels, column-step launches, interchange launches} */
+FAER_HIP_API void faer_hip_debug_clu_last(size_t out[4]);
 
 #ifdef __cplusplus
 }
