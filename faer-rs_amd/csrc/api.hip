@@ -932,675 +932,448 @@ void faer_hip_gemm(FaerHipDType dtype, FaerHipIType itype, size_t m, size_t n, s
 }
 
 // ---------------------------------------------------------------------------------------- outer boundary
-// complex level 3 (faer-ffi/src/lib.rs:855-937): the same templates on c32 / c64, the triangular solves honour their FaerConj
-#define X(suf)                                                                                                         \
-	void libfaer_v0_23_matmul_##suf(FaerMatMut C, FaerAccum accum, FaerMatRef A, FaerMatRef B, const void *alpha,    \
-					FaerPar par)                                                                        \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		matmul_api<suf>(C, accum, A, B, alpha);                                                                \
-	}                                                                                                              \
-	void libfaer_v0_23_matmul_triangular_##suf(FaerMatMut C, FaerBlock C_block, FaerAccum accum, FaerMatRef A,      \
-						   FaerBlock A_block, FaerMatRef B, FaerBlock B_block, const void *alpha,    \
-						   FaerPar par)                                                             \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		matmul_triangular_api<suf>(C, C_block, accum, A, A_block, B, B_block, alpha);                           \
-	}                                                                                                              \
-	void libfaer_v0_23_solve_triangular_lower_in_place_##suf(FaerMatRef L, FaerConj cj, FaerMatMut rhs, FaerPar par) \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		trsm_api<suf>(L, rhs, false, false, cj == FaerConj_Yes);                                               \
-	}                                                                                                              \
-	void libfaer_v0_23_solve_triangular_upper_in_place_##suf(FaerMatRef U, FaerConj cj, FaerMatMut rhs, FaerPar par) \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		trsm_api<suf>(U, rhs, true, false, cj == FaerConj_Yes);                                                \
-	}                                                                                                              \
-	void libfaer_v0_23_solve_unit_triangular_lower_in_place_##suf(FaerMatRef L, FaerConj cj, FaerMatMut rhs,        \
-								      FaerPar par)                                          \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		trsm_api<suf>(L, rhs, false, true, cj == FaerConj_Yes);                                                \
-	}                                                                                                              \
-	void libfaer_v0_23_solve_unit_triangular_upper_in_place_##suf(FaerMatRef U, FaerConj cj, FaerMatMut rhs,        \
-								      FaerPar par)                                          \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		trsm_api<suf>(U, rhs, true, true, cj == FaerConj_Yes);                                                 \
-	}
-X(c64)
-X(c32)
-#undef X
+// One short macro per family: defined, expanded over exactly the lists the family supports, undefined again.  Every wrapper is
+// checked against its prototype in include/faer_hip.h.  An argument that the device path does not use (par, mem, most params;
+// conj where a family is real only) is left unnamed.  Adding a scalar type to a family = adding it to that family's list.
+//
+// scalar lists: X(suf, T)
+#define FH_FOR_REAL(X) X(f64, double) X(f32, float)
+#define FH_FOR_COMPLEX(X) X(c64, c64) X(c32, c32)
+#define FH_FOR_SCALARS(X) FH_FOR_REAL(X) FH_FOR_COMPLEX(X)
+#define FH_FOR_DTYPES(X) FH_FOR_REAL(X)
+// index list: X(suf, T, it, I).  FH_FOR_INDEXED(LIST) expands the family's X over a scalar list times the index list.
+#define FH_FOR_INDICES(X, suf, T) X(suf, T, u32, uint32_t) X(suf, T, u64, uint64_t)
+#define FH_X_PER_INDEX(suf, T) FH_FOR_INDICES(X, suf, T)
+#define FH_FOR_INDEXED(LIST) LIST(FH_X_PER_INDEX)
 
-// complex partial-pivot LU (faer-ffi/src/lib.rs:1952-1984 and the solves): the templates of the real family on c32 / c64 (cgetrf.hip);
-// the solves honour A_conj.  The scratch queries are the reference's: indices for the factorization, one copy of rhs for a solve.
-#define X(suf, it, I)                                                                                                  \
-	FaerLayout libfaer_v0_23_partial_piv_lu_factor_in_place_scratch_##it##_##suf(size_t dim, size_t bs, FaerPar par, \
-										      FaerPartialPivLuParams params)        \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) params;                                                                                         \
-		return layout((dim < bs ? dim : bs) * sizeof(I), sizeof(I));                                           \
-	}                                                                                                              \
-	FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_##it##_##suf(                               \
-		FaerMatMut A, FaerSliceMut pf, FaerSliceMut pb, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params) \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		(void) params;                                                                                         \
-		return lu_api<suf, I>(A, pf, pb);                                                                      \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_##it##_##suf(size_t dim, size_t k, FaerPar par)  \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		return layout(dim * k * sizeof(suf), 64);                                                              \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_##it##_##suf(size_t dim, size_t k, FaerPar par) \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		return layout(dim * k * sizeof(suf), 64);                                                              \
-	}                                                                                                              \
-	void libfaer_v0_23_partial_piv_lu_solve_in_place_##it##_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef pf, \
-								      FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		lu_solve_api<suf, I>(L, U, pf, pb, rhs, false, cj == FaerConj_Yes);                                    \
-	}                                                                                                              \
-	void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_##it##_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, \
-										FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, \
-										FaerPar par, FaerMemAlloc mem)              \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		lu_solve_api<suf, I>(L, U, pf, pb, rhs, true, cj == FaerConj_Yes);                                     \
-	}
-X(c64, u32, uint32_t)
-X(c64, u64, uint64_t)
-X(c32, u32, uint32_t)
-X(c32, u64, uint64_t)
-#undef X
-FaerPartialPivLuParams libfaer_v0_23_PartialPivLuParams_c64(void) { return FaerPartialPivLuParams{16, 64, 128 * 128}; }
-FaerPartialPivLuParams libfaer_v0_23_PartialPivLuParams_c32(void) { return FaerPartialPivLuParams{16, 64, 128 * 128}; }
-
-#define FH_FOR_DTYPES(X) X(f64, double) X(f32, float)
-
+// level 3 (faer-ffi/src/lib.rs:855-937), real and complex: the triangular solves honour their FaerConj (the identity for a real T)
 #define X(suf, T)                                                                                                      \
-	void libfaer_v0_23_matmul_##suf(FaerMatMut C, FaerAccum accum, FaerMatRef A, FaerMatRef B, const void *alpha,    \
-					FaerPar par)                                                                        \
+	void libfaer_v0_23_matmul_##suf(FaerMatMut C, FaerAccum accum, FaerMatRef A, FaerMatRef B, const void *alpha,  \
+					FaerPar)                                                                       \
 	{                                                                                                              \
-		(void) par;                                                                                            \
 		matmul_api<T>(C, accum, A, B, alpha);                                                                  \
 	}                                                                                                              \
-	void libfaer_v0_23_matmul_triangular_##suf(FaerMatMut C, FaerBlock C_block, FaerAccum accum, FaerMatRef A,      \
-						   FaerBlock A_block, FaerMatRef B, FaerBlock B_block, const void *alpha,    \
-						   FaerPar par)                                                             \
+	void libfaer_v0_23_matmul_triangular_##suf(FaerMatMut C, FaerBlock C_block, FaerAccum accum, FaerMatRef A,     \
+						   FaerBlock A_block, FaerMatRef B, FaerBlock B_block,                 \
+						   const void *alpha, FaerPar)                                         \
 	{                                                                                                              \
-		(void) par;                                                                                            \
-		matmul_triangular_api<T>(C, C_block, accum, A, A_block, B, B_block, alpha);                             \
+		matmul_triangular_api<T>(C, C_block, accum, A, A_block, B, B_block, alpha);                            \
 	}                                                                                                              \
-	void libfaer_v0_23_solve_triangular_lower_in_place_##suf(FaerMatRef L, FaerConj cj, FaerMatMut rhs, FaerPar par) \
+	void libfaer_v0_23_solve_triangular_lower_in_place_##suf(FaerMatRef L, FaerConj cj, FaerMatMut rhs, FaerPar)   \
 	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		trsm_api<T>(L, rhs, false, false);                                                                     \
+		trsm_api<T>(L, rhs, false, false, cj == FaerConj_Yes);                                                 \
 	}                                                                                                              \
-	void libfaer_v0_23_solve_triangular_upper_in_place_##suf(FaerMatRef U, FaerConj cj, FaerMatMut rhs, FaerPar par) \
+	void libfaer_v0_23_solve_triangular_upper_in_place_##suf(FaerMatRef U, FaerConj cj, FaerMatMut rhs, FaerPar)   \
 	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		trsm_api<T>(U, rhs, true, false);                                                                      \
+		trsm_api<T>(U, rhs, true, false, cj == FaerConj_Yes);                                                  \
 	}                                                                                                              \
-	void libfaer_v0_23_solve_unit_triangular_lower_in_place_##suf(FaerMatRef L, FaerConj cj, FaerMatMut rhs,        \
-								      FaerPar par)                                          \
+	void libfaer_v0_23_solve_unit_triangular_lower_in_place_##suf(FaerMatRef L, FaerConj cj, FaerMatMut rhs,       \
+								      FaerPar)                                         \
 	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		trsm_api<T>(L, rhs, false, true);                                                                      \
+		trsm_api<T>(L, rhs, false, true, cj == FaerConj_Yes);                                                  \
 	}                                                                                                              \
-	void libfaer_v0_23_solve_unit_triangular_upper_in_place_##suf(FaerMatRef U, FaerConj cj, FaerMatMut rhs,        \
-								      FaerPar par)                                          \
+	void libfaer_v0_23_solve_unit_triangular_upper_in_place_##suf(FaerMatRef U, FaerConj cj, FaerMatMut rhs,       \
+								      FaerPar)                                         \
 	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		trsm_api<T>(U, rhs, true, true);                                                                       \
+		trsm_api<T>(U, rhs, true, true, cj == FaerConj_Yes);                                                   \
+	}
+FH_FOR_SCALARS(X)
+#undef X
+
+// triangular inverse (lib.rs:938-983)
+#define X(suf, T)                                                                                                      \
+	void libfaer_v0_23_inverse_triangular_lower_in_place_##suf(FaerMatMut T_inv, FaerMatRef Tm, FaerPar)           \
+	{                                                                                                              \
+		tri_inverse_api<T>(T_inv, Tm, false, false);                                                           \
 	}                                                                                                              \
-	FaerLltParams libfaer_v0_23_LltParams_##suf(void) { return FaerLltParams{64, 128}; }                            \
-	FaerLdltParams libfaer_v0_23_LdltParams_##suf(void) { return FaerLdltParams{64, 128}; }                         \
-	FaerLayout libfaer_v0_23_ldlt_factor_in_place_scratch_##suf(size_t dim, FaerPar par, FaerLdltParams params)     \
+	void libfaer_v0_23_inverse_triangular_upper_in_place_##suf(FaerMatMut T_inv, FaerMatRef Tm, FaerPar)           \
 	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) params;                                                                                         \
+		tri_inverse_api<T>(T_inv, Tm, true, false);                                                            \
+	}                                                                                                              \
+	void libfaer_v0_23_inverse_unit_triangular_lower_in_place_##suf(FaerMatMut T_inv, FaerMatRef Tm, FaerPar)      \
+	{                                                                                                              \
+		tri_inverse_api<T>(T_inv, Tm, false, true);                                                            \
+	}                                                                                                              \
+	void libfaer_v0_23_inverse_unit_triangular_upper_in_place_##suf(FaerMatMut T_inv, FaerMatRef Tm, FaerPar)      \
+	{                                                                                                              \
+		tri_inverse_api<T>(T_inv, Tm, true, true);                                                             \
+	}
+FH_FOR_REAL(X)
+#undef X
+
+// LLT (lib.rs:650-655 params, :984-1040 factor and solve, :1039-1075 reconstruct and inverse)
+#define X(suf, T)                                                                                                      \
+	FaerLltParams libfaer_v0_23_LltParams_##suf(void) { return FaerLltParams{64, 128}; }                           \
+	FaerLayout libfaer_v0_23_llt_factor_in_place_scratch_##suf(size_t dim, FaerPar, FaerLltParams)                 \
+	{                                                                                                              \
 		return layout(dim * sizeof(T), 64);                                                                    \
 	}                                                                                                              \
-	FaerLdltStatus libfaer_v0_23_ldlt_factor_in_place_##suf(FaerMatMut A, FaerLdltRegularization reg, FaerPar par,  \
-								FaerMemAlloc mem, FaerLdltParams params)                    \
+	FaerLltStatus libfaer_v0_23_llt_factor_in_place_##suf(FaerMatMut A, FaerLltRegularization reg, FaerPar,        \
+							      FaerMemAlloc, FaerLltParams)                             \
 	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		(void) params;                                                                                         \
-		return ldlt_api<T>(A, reg);                                                                            \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_ldlt_solve_in_place_scratch_##suf(size_t dim, size_t rhs_ncols, FaerPar par)           \
-	{                                                                                                              \
-		(void) dim;                                                                                            \
-		(void) rhs_ncols;                                                                                      \
-		(void) par;                                                                                            \
-		return layout(0, 1);                                                                                   \
-	}                                                                                                              \
-	void libfaer_v0_23_ldlt_solve_in_place_##suf(FaerMatRef L, FaerVecRef D, FaerConj cj, FaerMatMut rhs, FaerPar par, \
-						     FaerMemAlloc mem)                                                      \
-	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		ldlt_solve_api<T>(L, D, rhs);                                                                          \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_llt_factor_in_place_scratch_##suf(size_t dim, FaerPar par, FaerLltParams params)       \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) params;                                                                                         \
-		return layout(dim * sizeof(T), 64);                                                                    \
-	}                                                                                                              \
-	FaerLltStatus libfaer_v0_23_llt_factor_in_place_##suf(FaerMatMut A, FaerLltRegularization reg, FaerPar par,     \
-							      FaerMemAlloc mem, FaerLltParams params)                        \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		(void) params;                                                                                         \
 		return llt_api<T>(A, reg);                                                                             \
 	}                                                                                                              \
-	FaerLayout libfaer_v0_23_llt_solve_in_place_scratch_##suf(size_t dim, size_t rhs_ncols, FaerPar par)            \
+	FaerLayout libfaer_v0_23_llt_solve_in_place_scratch_##suf(size_t, size_t, FaerPar) { return layout(0, 1); }    \
+	void libfaer_v0_23_llt_solve_in_place_##suf(FaerMatRef L, FaerConj, FaerMatMut rhs, FaerPar, FaerMemAlloc)     \
 	{                                                                                                              \
-		(void) dim;                                                                                            \
-		(void) rhs_ncols;                                                                                      \
-		(void) par;                                                                                            \
-		return layout(0, 1);                                                                                   \
-	}                                                                                                              \
-	void libfaer_v0_23_llt_solve_in_place_##suf(FaerMatRef L, FaerConj cj, FaerMatMut rhs, FaerPar par,             \
-						    FaerMemAlloc mem)                                                       \
-	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
 		llt_solve_api<T>(L, rhs);                                                                              \
 	}                                                                                                              \
-	FaerPartialPivLuParams libfaer_v0_23_PartialPivLuParams_##suf(void)                                             \
+	FaerLayout libfaer_v0_23_llt_reconstruct_scratch_##suf(size_t, FaerPar) { return layout(0, 1); }               \
+	void libfaer_v0_23_llt_reconstruct_##suf(FaerMatMut A, FaerMatRef L, FaerPar, FaerMemAlloc)                    \
+	{                                                                                                              \
+		llt_reconstruct_api<T>(A, L);                                                                          \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_llt_inverse_scratch_##suf(size_t dim, FaerPar)                                        \
+	{                                                                                                              \
+		return layout(dim * dim * sizeof(T), 64);                                                              \
+	}                                                                                                              \
+	void libfaer_v0_23_llt_inverse_##suf(FaerMatMut A_inv, FaerMatRef L, FaerPar, FaerMemAlloc)                    \
+	{                                                                                                              \
+		llt_inverse_api<T>(A_inv, L);                                                                          \
+	}
+FH_FOR_REAL(X)
+#undef X
+
+// LDLT (lib.rs:660-664 params, :1189-1250 factor and solve, :1247-1288 reconstruct and inverse)
+#define X(suf, T)                                                                                                      \
+	FaerLdltParams libfaer_v0_23_LdltParams_##suf(void) { return FaerLdltParams{64, 128}; }                        \
+	FaerLayout libfaer_v0_23_ldlt_factor_in_place_scratch_##suf(size_t dim, FaerPar, FaerLdltParams)               \
+	{                                                                                                              \
+		return layout(dim * sizeof(T), 64);                                                                    \
+	}                                                                                                              \
+	FaerLdltStatus libfaer_v0_23_ldlt_factor_in_place_##suf(FaerMatMut A, FaerLdltRegularization reg, FaerPar,     \
+								FaerMemAlloc, FaerLdltParams)                          \
+	{                                                                                                              \
+		return ldlt_api<T>(A, reg);                                                                            \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_ldlt_solve_in_place_scratch_##suf(size_t, size_t, FaerPar) { return layout(0, 1); }   \
+	void libfaer_v0_23_ldlt_solve_in_place_##suf(FaerMatRef L, FaerVecRef D, FaerConj, FaerMatMut rhs, FaerPar,    \
+						     FaerMemAlloc)                                                     \
+	{                                                                                                              \
+		ldlt_solve_api<T>(L, D, rhs);                                                                          \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_ldlt_reconstruct_scratch_##suf(size_t dim, FaerPar)                                   \
+	{                                                                                                              \
+		return layout(dim * dim * sizeof(T), 64);                                                              \
+	}                                                                                                              \
+	void libfaer_v0_23_ldlt_reconstruct_##suf(FaerMatMut A, FaerMatRef L, FaerVecRef D, FaerPar, FaerMemAlloc)     \
+	{                                                                                                              \
+		ldlt_reconstruct_api<T>(A, L, D);                                                                      \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_ldlt_inverse_scratch_##suf(size_t dim, FaerPar)                                       \
+	{                                                                                                              \
+		return layout(dim * dim * sizeof(T), 64);                                                              \
+	}                                                                                                              \
+	void libfaer_v0_23_ldlt_inverse_##suf(FaerMatMut A_inv, FaerMatRef L, FaerVecRef D, FaerPar, FaerMemAlloc)     \
+	{                                                                                                              \
+		ldlt_inverse_api<T>(A_inv, L, D);                                                                      \
+	}
+FH_FOR_REAL(X)
+#undef X
+
+// partial-pivot LU, real and complex (lib.rs:679-685 params, :1952-1984 factor, :1985-2056 solves): the solves honour A_conj.
+// The scratch queries are the reference's: min(dim, block_size) indices for the factorization, one copy of rhs for a solve.
+#define X(suf, T)                                                                                                      \
+	FaerPartialPivLuParams libfaer_v0_23_PartialPivLuParams_##suf(void)                                            \
 	{                                                                                                              \
 		return FaerPartialPivLuParams{16, 64, 128 * 128};                                                      \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_partial_piv_lu_factor_in_place_scratch_u32_##suf(size_t dim, size_t bs, FaerPar par,   \
-										  FaerPartialPivLuParams params)            \
+	}
+FH_FOR_SCALARS(X)
+#undef X
+#define X(suf, T, it, I)                                                                                               \
+	FaerLayout libfaer_v0_23_partial_piv_lu_factor_in_place_scratch_##it##_##suf(size_t dim, size_t bs, FaerPar,   \
+										      FaerPartialPivLuParams)          \
 	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) params;                                                                                         \
-		return layout((dim < bs ? dim : bs) * 4, 4);                                                           \
+		return layout((dim < bs ? dim : bs) * sizeof(I), sizeof(I));                                           \
 	}                                                                                                              \
-	FaerLayout libfaer_v0_23_partial_piv_lu_factor_in_place_scratch_u64_##suf(size_t dim, size_t bs, FaerPar par,   \
-										  FaerPartialPivLuParams params)            \
+	FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_##it##_##suf(                              \
+		FaerMatMut A, FaerSliceMut pf, FaerSliceMut pb, FaerPar, FaerMemAlloc, FaerPartialPivLuParams)         \
 	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) params;                                                                                         \
-		return layout((dim < bs ? dim : bs) * 8, 8);                                                           \
+		return lu_api<T, I>(A, pf, pb);                                                                        \
 	}                                                                                                              \
-	FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_u32_##suf(                                  \
-		FaerMatMut A, FaerSliceMut pf, FaerSliceMut pb, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params) \
+	FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_##it##_##suf(size_t dim, size_t k, FaerPar)     \
 	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		(void) params;                                                                                         \
-		return lu_api<T, uint32_t>(A, pf, pb);                                                                 \
+		return layout(dim * k * sizeof(T), 64);                                                                \
 	}                                                                                                              \
-	FaerPartialPivLuStatus libfaer_v0_23_partial_piv_lu_factor_in_place_u64_##suf(                                  \
-		FaerMatMut A, FaerSliceMut pf, FaerSliceMut pb, FaerPar par, FaerMemAlloc mem, FaerPartialPivLuParams params) \
+	void libfaer_v0_23_partial_piv_lu_solve_in_place_##it##_##suf(                                                 \
+		FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, FaerPar,    \
+		FaerMemAlloc)                                                                                          \
 	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		(void) params;                                                                                         \
-		return lu_api<T, uint64_t>(A, pf, pb);                                                                 \
+		lu_solve_api<T, I>(L, U, pf, pb, rhs, false, cj == FaerConj_Yes);                                      \
 	}                                                                                                              \
-	FaerFullPivLuParams libfaer_v0_23_FullPivLuParams_##suf(void) \
-	{ \
-		return FaerFullPivLuParams{256 * 512}; \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_factor_in_place_scratch_u32_##suf(size_t dim, size_t bs, FaerPar par, FaerFullPivLuParams params) \
-	{ \
-		(void) bs; (void) par; (void) params; return layout(dim * 2 * sizeof(size_t), sizeof(size_t)); \
-	} \
-	FaerFullPivLuStatus libfaer_v0_23_full_piv_lu_factor_in_place_u32_##suf(FaerMatMut A, FaerSliceMut rpf, FaerSliceMut rpb, FaerSliceMut cpf, FaerSliceMut cpb, FaerPar par, FaerMemAlloc mem, FaerFullPivLuParams params) \
-	{ \
-		(void) par; (void) mem; (void) params; return full_lu_api<T, uint32_t>(A, rpf, rpb, cpf, cpb); \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_solve_in_place_scratch_u32_##suf(size_t dim, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_full_piv_lu_solve_in_place_u32_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf, FaerSliceRef cpb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; full_lu_solve_api<T, uint32_t>(L, U, rpf, rpb, cpf, cpb, rhs, false); \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_solve_transpose_in_place_scratch_u32_##suf(size_t dim, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_full_piv_lu_solve_transpose_in_place_u32_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf, FaerSliceRef cpb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; full_lu_solve_api<T, uint32_t>(L, U, rpf, rpb, cpf, cpb, rhs, true); \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_factor_in_place_scratch_u64_##suf(size_t dim, size_t bs, FaerPar par, FaerFullPivLuParams params) \
-	{ \
-		(void) bs; (void) par; (void) params; return layout(dim * 2 * sizeof(size_t), sizeof(size_t)); \
-	} \
-	FaerFullPivLuStatus libfaer_v0_23_full_piv_lu_factor_in_place_u64_##suf(FaerMatMut A, FaerSliceMut rpf, FaerSliceMut rpb, FaerSliceMut cpf, FaerSliceMut cpb, FaerPar par, FaerMemAlloc mem, FaerFullPivLuParams params) \
-	{ \
-		(void) par; (void) mem; (void) params; return full_lu_api<T, uint64_t>(A, rpf, rpb, cpf, cpb); \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_solve_in_place_scratch_u64_##suf(size_t dim, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_full_piv_lu_solve_in_place_u64_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf, FaerSliceRef cpb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; full_lu_solve_api<T, uint64_t>(L, U, rpf, rpb, cpf, cpb, rhs, false); \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_solve_transpose_in_place_scratch_u64_##suf(size_t dim, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_full_piv_lu_solve_transpose_in_place_u64_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf, FaerSliceRef cpb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; full_lu_solve_api<T, uint64_t>(L, U, rpf, rpb, cpf, cpb, rhs, true); \
-	} \
-	FaerColPivQrParams libfaer_v0_23_ColPivQrParams_##suf(void) \
-	{ \
-		return FaerColPivQrParams{48 * 48, 192 * 256}; \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_factor_in_place_scratch_u32_##suf(size_t nrows, size_t ncols, size_t bs, FaerPar par, FaerColPivQrParams params) \
-	{ \
-		(void) nrows; (void) bs; (void) par; (void) params; return layout(ncols * 2 * sizeof(T), 64); \
-	} \
-	FaerColPivQrStatus libfaer_v0_23_colpiv_qr_factor_in_place_u32_##suf(FaerMatMut A, FaerMatMut Q_coeff, FaerSliceMut pf, FaerSliceMut pb, FaerPar par, FaerMemAlloc mem, FaerColPivQrParams params) \
-	{ \
-		(void) par; (void) mem; (void) params; return colpiv_qr_api<T, uint32_t>(A, Q_coeff, pf, pb); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_solve_in_place_scratch_u32_##suf(size_t dim, size_t bs, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(bs * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_solve_in_place_u32_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj cj, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; colpiv_qr_solve_api<T, uint32_t>(Qb, Qc, R, pf, pb, rhs, false, true); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_solve_transpose_in_place_scratch_u32_##suf(size_t dim, size_t bs, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(bs * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_solve_transpose_in_place_u32_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj cj, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; colpiv_qr_solve_api<T, uint32_t>(Qb, Qc, R, pf, pb, rhs, true, true); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_solve_lstsq_in_place_scratch_u32_##suf(size_t nrows, size_t ncols, size_t bs, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(bs * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_solve_lstsq_in_place_u32_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj cj, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; colpiv_qr_solve_api<T, uint32_t>(Qb, Qc, R, pf, pb, rhs, false, false); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_factor_in_place_scratch_u64_##suf(size_t nrows, size_t ncols, size_t bs, FaerPar par, FaerColPivQrParams params) \
-	{ \
-		(void) nrows; (void) bs; (void) par; (void) params; return layout(ncols * 2 * sizeof(T), 64); \
-	} \
-	FaerColPivQrStatus libfaer_v0_23_colpiv_qr_factor_in_place_u64_##suf(FaerMatMut A, FaerMatMut Q_coeff, FaerSliceMut pf, FaerSliceMut pb, FaerPar par, FaerMemAlloc mem, FaerColPivQrParams params) \
-	{ \
-		(void) par; (void) mem; (void) params; return colpiv_qr_api<T, uint64_t>(A, Q_coeff, pf, pb); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_solve_in_place_scratch_u64_##suf(size_t dim, size_t bs, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(bs * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_solve_in_place_u64_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj cj, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; colpiv_qr_solve_api<T, uint64_t>(Qb, Qc, R, pf, pb, rhs, false, true); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_solve_transpose_in_place_scratch_u64_##suf(size_t dim, size_t bs, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(bs * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_solve_transpose_in_place_u64_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj cj, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; colpiv_qr_solve_api<T, uint64_t>(Qb, Qc, R, pf, pb, rhs, true, true); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_solve_lstsq_in_place_scratch_u64_##suf(size_t nrows, size_t ncols, size_t bs, size_t k, FaerPar par) \
-	{ \
-		(void) par; return layout(bs * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_solve_lstsq_in_place_u64_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj cj, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; colpiv_qr_solve_api<T, uint64_t>(Qb, Qc, R, pf, pb, rhs, false, false); \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_reconstruct_scratch_u32_##suf(size_t nrows, size_t ncols, FaerPar par) \
-	{ \
-		(void) par; return layout(nrows * ncols * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_full_piv_lu_reconstruct_u32_##suf(FaerMatMut A, FaerMatRef L, FaerMatRef U, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf, FaerSliceRef cpb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; full_lu_reconstruct_api<T, uint32_t>(A, L, U, rpf, rpb, cpf, cpb); \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_inverse_scratch_u32_##suf(size_t dim, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_full_piv_lu_inverse_u32_##suf(FaerMatMut A_inv, FaerMatRef L, FaerMatRef U, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf, FaerSliceRef cpb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; full_lu_inverse_api<T, uint32_t>(A_inv, L, U, rpf, rpb, cpf, cpb); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_reconstruct_scratch_u32_##suf(size_t nrows, size_t ncols, size_t bs, FaerPar par) \
-	{ \
-		(void) nrows; (void) par; return layout(bs * ncols * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_reconstruct_u32_##suf(FaerMatMut A, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerSliceRef pf, FaerSliceRef pb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; colpiv_qr_reconstruct_api<T, uint32_t>(A, Qb, Qc, R, pf, pb); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_inverse_scratch_u32_##suf(size_t dim, size_t bs, FaerPar par) \
-	{ \
-		(void) par; return layout(bs * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_inverse_u32_##suf(FaerMatMut A_inv, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerSliceRef pf, FaerSliceRef pb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; colpiv_qr_inverse_api<T, uint32_t>(A_inv, Qb, Qc, R, pf, pb); \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_reconstruct_scratch_u64_##suf(size_t nrows, size_t ncols, FaerPar par) \
-	{ \
-		(void) par; return layout(nrows * ncols * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_full_piv_lu_reconstruct_u64_##suf(FaerMatMut A, FaerMatRef L, FaerMatRef U, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf, FaerSliceRef cpb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; full_lu_reconstruct_api<T, uint64_t>(A, L, U, rpf, rpb, cpf, cpb); \
-	} \
-	FaerLayout libfaer_v0_23_full_piv_lu_inverse_scratch_u64_##suf(size_t dim, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_full_piv_lu_inverse_u64_##suf(FaerMatMut A_inv, FaerMatRef L, FaerMatRef U, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf, FaerSliceRef cpb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; full_lu_inverse_api<T, uint64_t>(A_inv, L, U, rpf, rpb, cpf, cpb); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_reconstruct_scratch_u64_##suf(size_t nrows, size_t ncols, size_t bs, FaerPar par) \
-	{ \
-		(void) nrows; (void) par; return layout(bs * ncols * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_reconstruct_u64_##suf(FaerMatMut A, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerSliceRef pf, FaerSliceRef pb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; colpiv_qr_reconstruct_api<T, uint64_t>(A, Qb, Qc, R, pf, pb); \
-	} \
-	FaerLayout libfaer_v0_23_colpiv_qr_inverse_scratch_u64_##suf(size_t dim, size_t bs, FaerPar par) \
-	{ \
-		(void) par; return layout(bs * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_colpiv_qr_inverse_u64_##suf(FaerMatMut A_inv, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerSliceRef pf, FaerSliceRef pb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; colpiv_qr_inverse_api<T, uint64_t>(A_inv, Qb, Qc, R, pf, pb); \
-	} \
-	void libfaer_v0_23_inverse_triangular_lower_in_place_##suf(FaerMatMut T_inv, FaerMatRef Tm, FaerPar par) \
-	{ \
-		(void) par; tri_inverse_api<T>(T_inv, Tm, false, false); \
-	} \
-	void libfaer_v0_23_inverse_triangular_upper_in_place_##suf(FaerMatMut T_inv, FaerMatRef Tm, FaerPar par) \
-	{ \
-		(void) par; tri_inverse_api<T>(T_inv, Tm, true, false); \
-	} \
-	void libfaer_v0_23_inverse_unit_triangular_lower_in_place_##suf(FaerMatMut T_inv, FaerMatRef Tm, FaerPar par) \
-	{ \
-		(void) par; tri_inverse_api<T>(T_inv, Tm, false, true); \
-	} \
-	void libfaer_v0_23_inverse_unit_triangular_upper_in_place_##suf(FaerMatMut T_inv, FaerMatRef Tm, FaerPar par) \
-	{ \
-		(void) par; tri_inverse_api<T>(T_inv, Tm, true, true); \
-	} \
-	FaerLayout libfaer_v0_23_llt_reconstruct_scratch_##suf(size_t dim, FaerPar par) \
-	{ \
-		(void) dim; (void) par; return layout(0, 1); \
-	} \
-	void libfaer_v0_23_llt_reconstruct_##suf(FaerMatMut A, FaerMatRef L, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; llt_reconstruct_api<T>(A, L); \
-	} \
-	FaerLayout libfaer_v0_23_llt_inverse_scratch_##suf(size_t dim, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_llt_inverse_##suf(FaerMatMut A_inv, FaerMatRef L, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; llt_inverse_api<T>(A_inv, L); \
-	} \
-	FaerLayout libfaer_v0_23_ldlt_reconstruct_scratch_##suf(size_t dim, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_ldlt_reconstruct_##suf(FaerMatMut A, FaerMatRef L, FaerVecRef D, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; ldlt_reconstruct_api<T>(A, L, D); \
-	} \
-	FaerLayout libfaer_v0_23_ldlt_inverse_scratch_##suf(size_t dim, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_ldlt_inverse_##suf(FaerMatMut A_inv, FaerMatRef L, FaerVecRef D, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; ldlt_inverse_api<T>(A_inv, L, D); \
-	} \
-	FaerLayout libfaer_v0_23_partial_piv_lu_reconstruct_scratch_u32_##suf(size_t nrows, size_t ncols, FaerPar par) \
-	{ \
-		(void) par; return layout(nrows * ncols * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_partial_piv_lu_reconstruct_u32_##suf(FaerMatMut A, FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; lu_reconstruct_api<T, uint32_t>(A, L, U, pf, pb); \
-	} \
-	FaerLayout libfaer_v0_23_partial_piv_lu_inverse_scratch_u32_##suf(size_t dim, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_partial_piv_lu_inverse_u32_##suf(FaerMatMut A_inv, FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; lu_inverse_api<T, uint32_t>(A_inv, L, U, pf, pb); \
-	} \
-	FaerLayout libfaer_v0_23_partial_piv_lu_reconstruct_scratch_u64_##suf(size_t nrows, size_t ncols, FaerPar par) \
-	{ \
-		(void) par; return layout(nrows * ncols * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_partial_piv_lu_reconstruct_u64_##suf(FaerMatMut A, FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; lu_reconstruct_api<T, uint64_t>(A, L, U, pf, pb); \
-	} \
-	FaerLayout libfaer_v0_23_partial_piv_lu_inverse_scratch_u64_##suf(size_t dim, FaerPar par) \
-	{ \
-		(void) par; return layout(dim * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_partial_piv_lu_inverse_u64_##suf(FaerMatMut A_inv, FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; lu_inverse_api<T, uint64_t>(A_inv, L, U, pf, pb); \
-	} \
-	FaerLayout libfaer_v0_23_qr_reconstruct_scratch_##suf(size_t nrows, size_t ncols, size_t bs, FaerPar par) \
-	{ \
-		(void) nrows; (void) par; return layout(bs * ncols * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_qr_reconstruct_##suf(FaerMatMut A, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; qr_reconstruct_api<T>(A, Qb, Qc, R); \
-	} \
-	FaerLayout libfaer_v0_23_qr_inverse_scratch_##suf(size_t dim, size_t bs, FaerPar par) \
-	{ \
-		(void) par; return layout(bs * dim * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_qr_inverse_##suf(FaerMatMut A_inv, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) par; (void) mem; qr_inverse_api<T>(A_inv, Qb, Qc, R); \
-	} \
-	FaerLayout libfaer_v0_23_apply_householder_on_the_right_scratch_##suf(size_t dim, size_t bs, size_t k) \
-	{ \
-		(void) dim; return layout(bs * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_apply_householder_on_the_right_##suf(FaerMatRef V, FaerMatRef H, FaerConj cj, FaerMatMut M, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; apply_hh_right_api<T>(V, H, M, false); \
-	} \
-	FaerLayout libfaer_v0_23_apply_householder_transpose_on_the_right_scratch_##suf(size_t dim, size_t bs, size_t k) \
-	{ \
-		(void) dim; return layout(bs * k * sizeof(T), 64); \
-	} \
-	void libfaer_v0_23_apply_householder_transpose_on_the_right_##suf(FaerMatRef V, FaerMatRef H, FaerConj cj, FaerMatMut M, FaerPar par, FaerMemAlloc mem) \
-	{ \
-		(void) cj; (void) par; (void) mem; apply_hh_right_api<T>(V, H, M, true); \
-	} \
-	FaerQrParams libfaer_v0_23_QrParams_##suf(void) { return FaerQrParams{48 * 48, 192 * 256}; }                    \
-	size_t libfaer_v0_23_qr_recommended_block_size_##suf(size_t nrows, size_t ncols)                                \
+	FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_##it##_##suf(size_t dim, size_t k,    \
+											       FaerPar)                \
+	{                                                                                                              \
+		return layout(dim * k * sizeof(T), 64);                                                                \
+	}                                                                                                              \
+	void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_##it##_##suf(                                       \
+		FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, FaerPar,    \
+		FaerMemAlloc)                                                                                          \
+	{                                                                                                              \
+		lu_solve_api<T, I>(L, U, pf, pb, rhs, true, cj == FaerConj_Yes);                                       \
+	}
+FH_FOR_INDEXED(FH_FOR_SCALARS)
+#undef X
+// reconstruct and inverse (lib.rs:2071-2124) are real only: the header declares no complex prototype for them
+#define X(suf, T, it, I)                                                                                               \
+	FaerLayout libfaer_v0_23_partial_piv_lu_reconstruct_scratch_##it##_##suf(size_t nrows, size_t ncols, FaerPar)  \
+	{                                                                                                              \
+		return layout(nrows * ncols * sizeof(T), 64);                                                          \
+	}                                                                                                              \
+	void libfaer_v0_23_partial_piv_lu_reconstruct_##it##_##suf(                                                    \
+		FaerMatMut A, FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, FaerPar, FaerMemAlloc)     \
+	{                                                                                                              \
+		lu_reconstruct_api<T, I>(A, L, U, pf, pb);                                                             \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_partial_piv_lu_inverse_scratch_##it##_##suf(size_t dim, FaerPar)                      \
+	{                                                                                                              \
+		return layout(dim * dim * sizeof(T), 64);                                                              \
+	}                                                                                                              \
+	void libfaer_v0_23_partial_piv_lu_inverse_##it##_##suf(                                                        \
+		FaerMatMut A_inv, FaerMatRef L, FaerMatRef U, FaerSliceRef pf, FaerSliceRef pb, FaerPar, FaerMemAlloc) \
+	{                                                                                                              \
+		lu_inverse_api<T, I>(A_inv, L, U, pf, pb);                                                             \
+	}
+FH_FOR_INDEXED(FH_FOR_REAL)
+#undef X
+
+// full-pivot LU (lib.rs:2125-2260 factor and solves, :2246-2330 reconstruct and inverse)
+#define X(suf, T)                                                                                                      \
+	FaerFullPivLuParams libfaer_v0_23_FullPivLuParams_##suf(void) { return FaerFullPivLuParams{256 * 512}; }
+FH_FOR_REAL(X)
+#undef X
+#define X(suf, T, it, I)                                                                                               \
+	FaerLayout libfaer_v0_23_full_piv_lu_factor_in_place_scratch_##it##_##suf(size_t dim, size_t, FaerPar,         \
+										   FaerFullPivLuParams)                \
+	{                                                                                                              \
+		return layout(dim * 2 * sizeof(size_t), sizeof(size_t));                                               \
+	}                                                                                                              \
+	FaerFullPivLuStatus libfaer_v0_23_full_piv_lu_factor_in_place_##it##_##suf(                                    \
+		FaerMatMut A, FaerSliceMut rpf, FaerSliceMut rpb, FaerSliceMut cpf, FaerSliceMut cpb, FaerPar,         \
+		FaerMemAlloc, FaerFullPivLuParams)                                                                     \
+	{                                                                                                              \
+		return full_lu_api<T, I>(A, rpf, rpb, cpf, cpb);                                                       \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_full_piv_lu_solve_in_place_scratch_##it##_##suf(size_t dim, size_t k, FaerPar)        \
+	{                                                                                                              \
+		return layout(dim * k * sizeof(T), 64);                                                                \
+	}                                                                                                              \
+	void libfaer_v0_23_full_piv_lu_solve_in_place_##it##_##suf(                                                    \
+		FaerMatRef L, FaerMatRef U, FaerConj, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf,            \
+		FaerSliceRef cpb, FaerMatMut rhs, FaerPar, FaerMemAlloc)                                               \
+	{                                                                                                              \
+		full_lu_solve_api<T, I>(L, U, rpf, rpb, cpf, cpb, rhs, false);                                         \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_full_piv_lu_solve_transpose_in_place_scratch_##it##_##suf(size_t dim, size_t k,       \
+											    FaerPar)                   \
+	{                                                                                                              \
+		return layout(dim * k * sizeof(T), 64);                                                                \
+	}                                                                                                              \
+	void libfaer_v0_23_full_piv_lu_solve_transpose_in_place_##it##_##suf(                                          \
+		FaerMatRef L, FaerMatRef U, FaerConj, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf,            \
+		FaerSliceRef cpb, FaerMatMut rhs, FaerPar, FaerMemAlloc)                                               \
+	{                                                                                                              \
+		full_lu_solve_api<T, I>(L, U, rpf, rpb, cpf, cpb, rhs, true);                                          \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_full_piv_lu_reconstruct_scratch_##it##_##suf(size_t nrows, size_t ncols, FaerPar)     \
+	{                                                                                                              \
+		return layout(nrows * ncols * sizeof(T), 64);                                                          \
+	}                                                                                                              \
+	void libfaer_v0_23_full_piv_lu_reconstruct_##it##_##suf(                                                       \
+		FaerMatMut A, FaerMatRef L, FaerMatRef U, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf,        \
+		FaerSliceRef cpb, FaerPar, FaerMemAlloc)                                                               \
+	{                                                                                                              \
+		full_lu_reconstruct_api<T, I>(A, L, U, rpf, rpb, cpf, cpb);                                            \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_full_piv_lu_inverse_scratch_##it##_##suf(size_t dim, FaerPar)                         \
+	{                                                                                                              \
+		return layout(dim * dim * sizeof(T), 64);                                                              \
+	}                                                                                                              \
+	void libfaer_v0_23_full_piv_lu_inverse_##it##_##suf(                                                           \
+		FaerMatMut A_inv, FaerMatRef L, FaerMatRef U, FaerSliceRef rpf, FaerSliceRef rpb, FaerSliceRef cpf,    \
+		FaerSliceRef cpb, FaerPar, FaerMemAlloc)                                                               \
+	{                                                                                                              \
+		full_lu_inverse_api<T, I>(A_inv, L, U, rpf, rpb, cpf, cpb);                                            \
+	}
+FH_FOR_INDEXED(FH_FOR_REAL)
+#undef X
+
+// Householder QR (lib.rs:667-671 params, :1520-1559 factor, :1560-1660 solves, :1661-1720 reconstruct and inverse)
+#define X(suf, T)                                                                                                      \
+	FaerQrParams libfaer_v0_23_QrParams_##suf(void) { return FaerQrParams{48 * 48, 192 * 256}; }                   \
+	size_t libfaer_v0_23_qr_recommended_block_size_##suf(size_t nrows, size_t ncols)                               \
 	{                                                                                                              \
 		return qr_block_size(nrows, ncols);                                                                    \
 	}                                                                                                              \
-	FaerLayout libfaer_v0_23_qr_factor_in_place_scratch_##suf(size_t nrows, size_t ncols, size_t bs, FaerPar par,   \
-								  FaerQrParams params)                                      \
+	FaerLayout libfaer_v0_23_qr_factor_in_place_scratch_##suf(size_t, size_t ncols, size_t bs, FaerPar,            \
+								  FaerQrParams)                                        \
 	{                                                                                                              \
-		(void) nrows;                                                                                          \
-		(void) par;                                                                                            \
-		(void) params;                                                                                         \
 		return layout(bs * ncols * sizeof(T), 64);                                                             \
 	}                                                                                                              \
-	FaerQrStatus libfaer_v0_23_qr_factor_in_place_##suf(FaerMatMut A, FaerMatMut Q, FaerPar par, FaerMemAlloc mem,  \
-							    FaerQrParams params)                                            \
+	FaerQrStatus libfaer_v0_23_qr_factor_in_place_##suf(FaerMatMut A, FaerMatMut Q, FaerPar, FaerMemAlloc,         \
+							    FaerQrParams params)                                       \
 	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
 		return qr_api<T>(A, Q, params);                                                                        \
 	}                                                                                                              \
-	FaerLayout libfaer_v0_23_apply_householder_on_the_left_scratch_##suf(size_t dim, size_t bs, size_t k)           \
+	FaerLayout libfaer_v0_23_qr_solve_in_place_scratch_##suf(size_t, size_t bs, size_t k, FaerPar)                 \
 	{                                                                                                              \
-		(void) dim;                                                                                            \
 		return layout(bs * k * sizeof(T), 64);                                                                 \
 	}                                                                                                              \
-	void libfaer_v0_23_apply_householder_on_the_left_##suf(FaerMatRef V, FaerMatRef H, FaerConj cj, FaerMatMut rhs, \
-							       FaerPar par, FaerMemAlloc mem)                               \
+	void libfaer_v0_23_qr_solve_in_place_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj,               \
+						   FaerMatMut rhs, FaerPar, FaerMemAlloc)                              \
 	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		apply_hh_api<T>(V, H, rhs, false);                                                                     \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_apply_householder_transpose_on_the_left_scratch_##suf(size_t dim, size_t bs, size_t k) \
-	{                                                                                                              \
-		(void) dim;                                                                                            \
-		return layout(bs * k * sizeof(T), 64);                                                                 \
-	}                                                                                                              \
-	void libfaer_v0_23_apply_householder_transpose_on_the_left_##suf(FaerMatRef V, FaerMatRef H, FaerConj cj,       \
-									 FaerMatMut rhs, FaerPar par, FaerMemAlloc mem)     \
-	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		apply_hh_api<T>(V, H, rhs, true);                                                                      \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_u32_##suf(size_t dim, size_t k, FaerPar par)     \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		return layout(dim * k * sizeof(T), 64);                                                                \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_partial_piv_lu_solve_in_place_scratch_u64_##suf(size_t dim, size_t k, FaerPar par)     \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		return layout(dim * k * sizeof(T), 64);                                                                \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_u32_##suf(size_t dim, size_t k, FaerPar par) \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		return layout(dim * k * sizeof(T), 64);                                                                \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_scratch_u64_##suf(size_t dim, size_t k, FaerPar par) \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		return layout(dim * k * sizeof(T), 64);                                                                \
-	}                                                                                                              \
-	void libfaer_v0_23_partial_piv_lu_solve_in_place_u32_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef pf, \
-								   FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		lu_solve_api<T, uint32_t>(L, U, pf, pb, rhs, false);                                                   \
-	}                                                                                                              \
-	void libfaer_v0_23_partial_piv_lu_solve_in_place_u64_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj, FaerSliceRef pf, \
-								   FaerSliceRef pb, FaerMatMut rhs, FaerPar par, FaerMemAlloc mem) \
-	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		lu_solve_api<T, uint64_t>(L, U, pf, pb, rhs, false);                                                   \
-	}                                                                                                              \
-	void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_u32_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj,   \
-									     FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, \
-									     FaerPar par, FaerMemAlloc mem)                \
-	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		lu_solve_api<T, uint32_t>(L, U, pf, pb, rhs, true);                                                    \
-	}                                                                                                              \
-	void libfaer_v0_23_partial_piv_lu_solve_transpose_in_place_u64_##suf(FaerMatRef L, FaerMatRef U, FaerConj cj,   \
-									     FaerSliceRef pf, FaerSliceRef pb, FaerMatMut rhs, \
-									     FaerPar par, FaerMemAlloc mem)                \
-	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		lu_solve_api<T, uint64_t>(L, U, pf, pb, rhs, true);                                                    \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_qr_solve_in_place_scratch_##suf(size_t dim, size_t bs, size_t k, FaerPar par)          \
-	{                                                                                                              \
-		(void) dim;                                                                                            \
-		(void) par;                                                                                            \
-		return layout(bs * k * sizeof(T), 64);                                                                 \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_qr_solve_transpose_in_place_scratch_##suf(size_t dim, size_t bs, size_t k, FaerPar par) \
-	{                                                                                                              \
-		(void) dim;                                                                                            \
-		(void) par;                                                                                            \
-		return layout(bs * k * sizeof(T), 64);                                                                 \
-	}                                                                                                              \
-	FaerLayout libfaer_v0_23_qr_solve_lstsq_in_place_scratch_##suf(size_t nrows, size_t ncols, size_t bs, size_t k, \
-								       FaerPar par)                                         \
-	{                                                                                                              \
-		(void) nrows;                                                                                          \
-		(void) ncols;                                                                                          \
-		(void) par;                                                                                            \
-		return layout(bs * k * sizeof(T), 64);                                                                 \
-	}                                                                                                              \
-	void libfaer_v0_23_qr_solve_in_place_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj cj, FaerMatMut rhs, \
-						   FaerPar par, FaerMemAlloc mem)                                           \
-	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
 		qr_solve_api<T>(Qb, Qc, R, rhs, false, true);                                                          \
 	}                                                                                                              \
-	void libfaer_v0_23_qr_solve_transpose_in_place_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj cj,   \
-							     FaerMatMut rhs, FaerPar par, FaerMemAlloc mem)                 \
+	FaerLayout libfaer_v0_23_qr_solve_transpose_in_place_scratch_##suf(size_t, size_t bs, size_t k, FaerPar)       \
 	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
+		return layout(bs * k * sizeof(T), 64);                                                                 \
+	}                                                                                                              \
+	void libfaer_v0_23_qr_solve_transpose_in_place_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj,     \
+							     FaerMatMut rhs, FaerPar, FaerMemAlloc)                    \
+	{                                                                                                              \
 		qr_solve_api<T>(Qb, Qc, R, rhs, true, true);                                                           \
 	}                                                                                                              \
-	void libfaer_v0_23_qr_solve_lstsq_in_place_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj cj,       \
-							 FaerMatMut rhs, FaerPar par, FaerMemAlloc mem)                     \
+	FaerLayout libfaer_v0_23_qr_solve_lstsq_in_place_scratch_##suf(size_t, size_t, size_t bs, size_t k, FaerPar)   \
 	{                                                                                                              \
-		(void) cj;                                                                                             \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
+		return layout(bs * k * sizeof(T), 64);                                                                 \
+	}                                                                                                              \
+	void libfaer_v0_23_qr_solve_lstsq_in_place_##suf(FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj,         \
+							 FaerMatMut rhs, FaerPar, FaerMemAlloc)                        \
+	{                                                                                                              \
 		qr_solve_api<T>(Qb, Qc, R, rhs, false, false);                                                         \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_qr_reconstruct_scratch_##suf(size_t, size_t ncols, size_t bs, FaerPar)                \
+	{                                                                                                              \
+		return layout(bs * ncols * sizeof(T), 64);                                                             \
+	}                                                                                                              \
+	void libfaer_v0_23_qr_reconstruct_##suf(FaerMatMut A, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerPar,     \
+						FaerMemAlloc)                                                          \
+	{                                                                                                              \
+		qr_reconstruct_api<T>(A, Qb, Qc, R);                                                                   \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_qr_inverse_scratch_##suf(size_t dim, size_t bs, FaerPar)                              \
+	{                                                                                                              \
+		return layout(bs * dim * sizeof(T), 64);                                                               \
+	}                                                                                                              \
+	void libfaer_v0_23_qr_inverse_##suf(FaerMatMut A_inv, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerPar,     \
+					    FaerMemAlloc)                                                              \
+	{                                                                                                              \
+		qr_inverse_api<T>(A_inv, Qb, Qc, R);                                                                   \
 	}
-FH_FOR_DTYPES(X)
+FH_FOR_REAL(X)
+#undef X
+
+// Householder application (lib.rs:1423-1470 on the left, :1471-1518 on the right)
+#define X(suf, T)                                                                                                      \
+	FaerLayout libfaer_v0_23_apply_householder_on_the_left_scratch_##suf(size_t, size_t bs, size_t k)              \
+	{                                                                                                              \
+		return layout(bs * k * sizeof(T), 64);                                                                 \
+	}                                                                                                              \
+	void libfaer_v0_23_apply_householder_on_the_left_##suf(FaerMatRef V, FaerMatRef H, FaerConj, FaerMatMut rhs,   \
+							       FaerPar, FaerMemAlloc)                                  \
+	{                                                                                                              \
+		apply_hh_api<T>(V, H, rhs, false);                                                                     \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_apply_householder_transpose_on_the_left_scratch_##suf(size_t, size_t bs, size_t k)    \
+	{                                                                                                              \
+		return layout(bs * k * sizeof(T), 64);                                                                 \
+	}                                                                                                              \
+	void libfaer_v0_23_apply_householder_transpose_on_the_left_##suf(FaerMatRef V, FaerMatRef H, FaerConj,         \
+									 FaerMatMut rhs, FaerPar, FaerMemAlloc)        \
+	{                                                                                                              \
+		apply_hh_api<T>(V, H, rhs, true);                                                                      \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_apply_householder_on_the_right_scratch_##suf(size_t, size_t bs, size_t k)             \
+	{                                                                                                              \
+		return layout(bs * k * sizeof(T), 64);                                                                 \
+	}                                                                                                              \
+	void libfaer_v0_23_apply_householder_on_the_right_##suf(FaerMatRef V, FaerMatRef H, FaerConj, FaerMatMut M,    \
+								FaerPar, FaerMemAlloc)                                 \
+	{                                                                                                              \
+		apply_hh_right_api<T>(V, H, M, false);                                                                 \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_apply_householder_transpose_on_the_right_scratch_##suf(size_t, size_t bs, size_t k)   \
+	{                                                                                                              \
+		return layout(bs * k * sizeof(T), 64);                                                                 \
+	}                                                                                                              \
+	void libfaer_v0_23_apply_householder_transpose_on_the_right_##suf(FaerMatRef V, FaerMatRef H, FaerConj,        \
+									  FaerMatMut M, FaerPar, FaerMemAlloc)         \
+	{                                                                                                              \
+		apply_hh_right_api<T>(V, H, M, true);                                                                  \
+	}
+FH_FOR_REAL(X)
+#undef X
+
+// column-pivot QR (lib.rs:1721-1876 factor and solves, :1877-1950 reconstruct and inverse)
+#define X(suf, T)                                                                                                      \
+	FaerColPivQrParams libfaer_v0_23_ColPivQrParams_##suf(void) { return FaerColPivQrParams{48 * 48, 192 * 256}; }
+FH_FOR_REAL(X)
+#undef X
+#define X(suf, T, it, I)                                                                                               \
+	FaerLayout libfaer_v0_23_colpiv_qr_factor_in_place_scratch_##it##_##suf(size_t, size_t ncols, size_t, FaerPar, \
+										 FaerColPivQrParams)                   \
+	{                                                                                                              \
+		return layout(ncols * 2 * sizeof(T), 64);                                                              \
+	}                                                                                                              \
+	FaerColPivQrStatus libfaer_v0_23_colpiv_qr_factor_in_place_##it##_##suf(                                       \
+		FaerMatMut A, FaerMatMut Q_coeff, FaerSliceMut pf, FaerSliceMut pb, FaerPar, FaerMemAlloc,             \
+		FaerColPivQrParams)                                                                                    \
+	{                                                                                                              \
+		return colpiv_qr_api<T, I>(A, Q_coeff, pf, pb);                                                        \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_colpiv_qr_solve_in_place_scratch_##it##_##suf(size_t, size_t bs, size_t k, FaerPar)   \
+	{                                                                                                              \
+		return layout(bs * k * sizeof(T), 64);                                                                 \
+	}                                                                                                              \
+	void libfaer_v0_23_colpiv_qr_solve_in_place_##it##_##suf(                                                      \
+		FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj, FaerSliceRef pf, FaerSliceRef pb,                \
+		FaerMatMut rhs, FaerPar, FaerMemAlloc)                                                                 \
+	{                                                                                                              \
+		colpiv_qr_solve_api<T, I>(Qb, Qc, R, pf, pb, rhs, false, true);                                        \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_colpiv_qr_solve_transpose_in_place_scratch_##it##_##suf(size_t, size_t bs, size_t k,  \
+											  FaerPar)                     \
+	{                                                                                                              \
+		return layout(bs * k * sizeof(T), 64);                                                                 \
+	}                                                                                                              \
+	void libfaer_v0_23_colpiv_qr_solve_transpose_in_place_##it##_##suf(                                            \
+		FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj, FaerSliceRef pf, FaerSliceRef pb,                \
+		FaerMatMut rhs, FaerPar, FaerMemAlloc)                                                                 \
+	{                                                                                                              \
+		colpiv_qr_solve_api<T, I>(Qb, Qc, R, pf, pb, rhs, true, true);                                         \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_colpiv_qr_solve_lstsq_in_place_scratch_##it##_##suf(size_t, size_t, size_t bs,        \
+										      size_t k, FaerPar)               \
+	{                                                                                                              \
+		return layout(bs * k * sizeof(T), 64);                                                                 \
+	}                                                                                                              \
+	void libfaer_v0_23_colpiv_qr_solve_lstsq_in_place_##it##_##suf(                                                \
+		FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerConj, FaerSliceRef pf, FaerSliceRef pb,                \
+		FaerMatMut rhs, FaerPar, FaerMemAlloc)                                                                 \
+	{                                                                                                              \
+		colpiv_qr_solve_api<T, I>(Qb, Qc, R, pf, pb, rhs, false, false);                                       \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_colpiv_qr_reconstruct_scratch_##it##_##suf(size_t, size_t ncols, size_t bs, FaerPar)  \
+	{                                                                                                              \
+		return layout(bs * ncols * sizeof(T), 64);                                                             \
+	}                                                                                                              \
+	void libfaer_v0_23_colpiv_qr_reconstruct_##it##_##suf(                                                         \
+		FaerMatMut A, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerSliceRef pf, FaerSliceRef pb, FaerPar,   \
+		FaerMemAlloc)                                                                                          \
+	{                                                                                                              \
+		colpiv_qr_reconstruct_api<T, I>(A, Qb, Qc, R, pf, pb);                                                 \
+	}                                                                                                              \
+	FaerLayout libfaer_v0_23_colpiv_qr_inverse_scratch_##it##_##suf(size_t dim, size_t bs, FaerPar)                \
+	{                                                                                                              \
+		return layout(bs * dim * sizeof(T), 64);                                                               \
+	}                                                                                                              \
+	void libfaer_v0_23_colpiv_qr_inverse_##it##_##suf(                                                             \
+		FaerMatMut A_inv, FaerMatRef Qb, FaerMatRef Qc, FaerMatRef R, FaerSliceRef pf, FaerSliceRef pb,        \
+		FaerPar, FaerMemAlloc)                                                                                 \
+	{                                                                                                              \
+		colpiv_qr_inverse_api<T, I>(A_inv, Qb, Qc, R, pf, pb);                                                 \
+	}
+FH_FOR_INDEXED(FH_FOR_REAL)
 #undef X
 
 FaerPar libfaer_v0_23_get_global_par(void)
@@ -1872,29 +1645,29 @@ void faer_hip_bidiag_in_place_f32(FaerMatMut A, FaerMatMut Hl, FaerMatMut Hr) { 
 void faer_hip_hessenberg_in_place_f64(FaerMatMut A, FaerMatMut householder) { hessenberg_api<double>(A, householder); }
 void faer_hip_hessenberg_in_place_f32(FaerMatMut A, FaerMatMut householder) { hessenberg_api<float>(A, householder); }
 
+// Cholesky update and deletion (cholesky/llt/update.rs:360-379, cholesky/ldlt/update.rs:376-434; no faer-ffi entry points)
 #define X(suf, T)                                                                                                      \
 	FaerLltStatus faer_hip_llt_rank_r_update_clobber_##suf(FaerMatMut L, FaerMatMut W, FaerVecMut alpha)           \
 	{                                                                                                              \
 		return chol_update_api<T>(L, W, alpha, false);                                                         \
 	}                                                                                                              \
-	void faer_hip_ldlt_rank_r_update_clobber_##suf(FaerMatMut LD, FaerMatMut W, FaerVecMut alpha) { (void) chol_update_api<T>(LD, W, alpha, true); } \
-	void faer_hip_ldlt_delete_rows_and_cols_clobber_u32_##suf(FaerMatMut LD, FaerSliceMut indices, FaerPar par, FaerMemAlloc mem) \
+	void faer_hip_ldlt_rank_r_update_clobber_##suf(FaerMatMut LD, FaerMatMut W, FaerVecMut alpha)                  \
 	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		ldlt_delete_api<T, uint32_t>(LD, indices);                                                             \
-	}                                                                                                              \
-	void faer_hip_ldlt_delete_rows_and_cols_clobber_u64_##suf(FaerMatMut LD, FaerSliceMut indices, FaerPar par, FaerMemAlloc mem) \
-	{                                                                                                              \
-		(void) par;                                                                                            \
-		(void) mem;                                                                                            \
-		ldlt_delete_api<T, uint64_t>(LD, indices);                                                             \
+		(void) chol_update_api<T>(LD, W, alpha, true);                                                         \
 	}                                                                                                              \
 	FaerLayout faer_hip_ldlt_delete_rows_and_cols_clobber_scratch_##suf(size_t dim, size_t n_removed)              \
 	{                                                                                                              \
-		return layout((dim * n_removed + n_removed) * sizeof(T), 64); /* ldlt/update.rs:402-408 */              \
+		return layout((dim * n_removed + n_removed) * sizeof(T), 64); /* ldlt/update.rs:402-408 */             \
 	}
 FH_FOR_DTYPES(X)
+#undef X
+#define X(suf, T, it, I)                                                                                               \
+	void faer_hip_ldlt_delete_rows_and_cols_clobber_##it##_##suf(FaerMatMut LD, FaerSliceMut indices, FaerPar,     \
+								     FaerMemAlloc)                                     \
+	{                                                                                                              \
+		ldlt_delete_api<T, I>(LD, indices);                                                                    \
+	}
+FH_FOR_INDEXED(FH_FOR_DTYPES)
 #undef X
 void faer_hip_debug_chol_update_last(long out[4]) { chol_update_last(out); }
 void faer_hip_debug_chol_update_diag_only(int on) { chol_update_debug_diag_only(on); }
