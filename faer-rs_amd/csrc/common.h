@@ -82,7 +82,6 @@ struct Ctx {
 		hipStream_t owner; // stream whose work last used the buffer: reuse is stream ordered only on that stream
 	};
 	std::vector<Buf> pool;
-	int *status = nullptr; // 16 ints of device status words
 	int *host_ints = nullptr; // 16 pinned host ints: read-back target of the drivers that return a status per call
 	int *pinned_ints();
 	// Look-ahead execution (factorizations): two internal streams on DISJOINT sets of CUs
@@ -156,7 +155,7 @@ void prof_collect(double *out, double *spans = nullptr, size_t cap = 0, size_t *
 double xwg_hop_us(int iters); // idle-chip hand-off latency between two workgroups, microseconds (ctx.hip)
 void debug_scratch_fill(int byte_or_minus_one); // debug: every scratch buffer handed out is filled with this byte first (-1 = off, the default; ctx.hip)
 void debug_scratch_fill_stats(size_t out[2]);  // {fills, bytes filled} since the last debug_scratch_fill
-void ctx_shutdown(); // releases the calling thread's look-ahead streams / events; safe without a device
+void ctx_shutdown(); // releases the calling thread's look-ahead streams / events, pinned ints and free scratch buffers (the context stays usable); safe without a device
 
 // stream `s` waits for event `e`
 inline void stream_wait(hipStream_t s, hipEvent_t e) { FH_HIP(hipStreamWaitEvent(s, e, 0)); }

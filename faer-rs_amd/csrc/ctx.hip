@@ -45,6 +45,21 @@ void ctx_shutdown()
 		(void) hipHostFree(c.host_ints);
 		c.host_ints = nullptr;
 	}
+	// the scratch pool: a thread that ends would otherwise keep one set of device buffers until the process ends (Ctx has no
+	// destructor -- a thread_local destructor would call HIP after the runtime is gone).  The caller's stream and the library's own
+	// streams are idle here; a free buffer whose owner is ANOTHER stream of the caller is covered by hipFree itself, which waits for
+	// the device (so a shutdown is a device-wide synchronisation point: other threads' queued work drains first).  Buffers in use (a
+	// Scratch alive further up this thread's stack) stay.  The device status words of the drivers are pool buffers too: the context
+	// owns no other device memory.  The context remains usable: the next call allocates again.
+	for (size_t i = 0; i < c.pool.size();) {
+		if (!c.pool[i].used) {
+			(void) hipFree(c.pool[i].p);
+			c.pool.erase(c.pool.begin() + i);
+		} else
+			++i;
+	}
+	if (c.pool.empty())
+		c.pool.shrink_to_fit();
 }
 
 int Ctx::stream_cus()
