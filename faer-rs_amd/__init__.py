@@ -358,7 +358,7 @@ def _dtype_suffix(x):
             return "c64", C64, 16
         if x.dtype == np.complex64:
             return "c32", C32, 8
-    raise TypeError(f"faer_rs_amd supports f32 / f64 (and c32 / c64 in matmul, matmul_triangular, gemm, the triangular solves and the "
+    raise TypeError(f"faer_rs_amd supports f32 / f64 (and c32 / c64 in matmul, matmul_triangular, gemm, the triangular solves and inverses and the "
                     f"partial-pivot LU with its solves), got {x.dtype}")
 
 
@@ -1160,7 +1160,8 @@ def _diag_vec(ld):
 
 def inverse_triangular_in_place(t_inv, t, upper=False, unit=False, par=PAR_SEQ):
     """triangular_inverse.rs: the (unit) lower / upper triangle of t_inv <- inverse of the triangle of t; the rest of
-    t_inv (and, unit: its diagonal) is left untouched"""
+    t_inv (and, unit: its diagonal) is left untouched.  float32 / float64 and complex64 / complex128 (interleaved); the other
+    triangle of t (and, unit: its diagonal) is never read"""
     suf, _, _ = _dtype_suffix(t)
     name = f"inverse_{'unit_' if unit else ''}triangular_{'upper' if upper else 'lower'}_in_place"
     getattr(lib(), f"libfaer_v0_23_{name}_{suf}")(_mat(t_inv, MatMut), _mat(t), par)
@@ -1388,6 +1389,15 @@ def debug_clu_last():
     out = (C.c_size_t * 4)()
     lib().faer_hip_debug_clu_last(out)
     return dict(zip(("leaf_panels", "step_panels", "step_launches", "swap_launches"), (int(v) for v in out)))
+
+
+def debug_ctrtri_shape(dtype):
+    """(E, sub_blocks) of the complex triangular inverse: the edge of its LDS-resident leaf and the number of sub-blocks along that
+    edge (the leaf inverts E // sub_blocks-wide diagonal sub-blocks by substitution and combines them by doubling); dtype complex64 or
+    complex128.  Needs no GPU."""
+    out = (C.c_size_t * 2)()
+    lib().faer_hip_debug_ctrtri_shape(C.c_int(np.dtype(dtype).itemsize), out)
+    return int(out[0]), int(out[1])
 
 
 def debug_scratch_fill(byte=-1):

@@ -998,7 +998,7 @@ FH_FOR_SCALARS(X)
 	{                                                                                                              \
 		tri_inverse_api<T>(T_inv, Tm, true, true);                                                             \
 	}
-FH_FOR_REAL(X)
+FH_FOR_SCALARS(X)
 #undef X
 
 // LLT (lib.rs:650-655 params, :984-1040 factor and solve, :1039-1075 reconstruct and inverse)

@@ -46,7 +46,7 @@ static __device__ __forceinline__ double fh_fma(double a, double b, double c) { 
 static __device__ __forceinline__ float fh_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
 // complex scalars of the boundary: faer's c32 / c64 are repr(C) {re, im}, interleaved (strides stay in complex elements).
-// Level 3 (cgemm.hip, ctrsm.hip) and the partial-pivot LU (cgetrf.hip) know them; everything else in the tree is instantiated for
+// Level 3 (cgemm.hip, ctrsm.hip, ctrtri.hip) and the partial-pivot LU (cgetrf.hip) know them; everything else in the tree is instantiated for
 // float / double.
 template <typename R> struct Cx {
 	R re, im;
@@ -460,6 +460,10 @@ template <> void gemm_dev<c32>(MatV<c32> C, DstKind kind, bool add, MatV<const c
 template <> void gemm_dev<c64>(MatV<c64> C, DstKind kind, bool add, MatV<const c64> A, MatV<const c64> B, c64 alpha, const GemmExtra<c64> *extra);
 template <> void matmul_triangular_dev<c32>(MatV<c32> C, int c_s, bool add, MatV<const c32> A, int a_s, MatV<const c32> B, int b_s, c32 alpha);
 template <> void matmul_triangular_dev<c64>(MatV<c64> C, int c_s, bool add, MatV<const c64> A, int a_s, MatV<const c64> B, int b_s, c64 alpha);
+// complex scalars (ctrtri.hip): the recursion of extras.hip on an LDS-resident complex leaf and the two drivers above
+template <> void tri_invert_lower_dev<c32>(MatV<c32> dst, MatV<const c32> src, bool unit);
+template <> void tri_invert_lower_dev<c64>(MatV<c64> dst, MatV<const c64> src, bool unit);
+void ctrtri_shape(int elem_bytes, size_t out[2]); // {E: edge of a leaf, sub-blocks along that edge}; elem_bytes 8 (c32) or 16 (c64)
 
 // X <- op(T)^-1 X, T lower triangular n x n, X n x k (trsm.hip); upper handled by reversal
 template <typename T> void trsm_lower_dev(MatV<const T> L, bool unit, MatV<T> X);

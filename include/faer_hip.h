@@ -225,8 +225,8 @@ FAER_HIP_API void faer_hip_gemm(FaerHipDType dtype, FaerHipIType itype, size_t m
 
 /* ---------------------------------------------------------------------------------------------
  * 2. OUTER boundary -- faer-ffi symbol-compatible entry points (f32 / f64; level 3 -- matmul, matmul_triangular and the
- *    four triangular solves -- and the partial-pivot LU with its two solves also c32 / c64, where the FaerConj argument of
- *    the solves is honoured).
+ *    four triangular solves --, the four triangular inverses and the partial-pivot LU with its two solves also c32 / c64,
+ *    where the FaerConj argument of the solves is honoured).
  *    Each comment cites the Rust function in faer-ffi/src/lib.rs it replaces.
  * --------------------------------------------------------------------------------------------- */
 /* A client that includes the reference's own faer-ffi/faer.h for these prototypes (tests/cabi_client/) defines
@@ -260,6 +260,16 @@ FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_upper_in_place_f64(FaerMat
 FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_upper_in_place_f32(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_upper_in_place_c64(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
 FAER_HIP_API void libfaer_v0_23_solve_unit_triangular_upper_in_place_c32(FaerMatRef U, FaerConj U_conj, FaerMatMut rhs, FaerPar par);
+/* lib.rs:938-983  la::triangular_inverse::invert_{,unit_}{lower,upper}_triangular for c32 / c64 (ctrtri.hip; the f32 / f64 prototypes
+ * are in section 2b).  Only the named triangle of T is read and of T_inv written; unit: neither diagonal is touched. */
+FAER_HIP_API void libfaer_v0_23_inverse_triangular_lower_in_place_c64(FaerMatMut T_inv, FaerMatRef T, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_inverse_triangular_lower_in_place_c32(FaerMatMut T_inv, FaerMatRef T, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_inverse_triangular_upper_in_place_c64(FaerMatMut T_inv, FaerMatRef T, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_inverse_triangular_upper_in_place_c32(FaerMatMut T_inv, FaerMatRef T, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_inverse_unit_triangular_lower_in_place_c64(FaerMatMut T_inv, FaerMatRef T, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_inverse_unit_triangular_lower_in_place_c32(FaerMatMut T_inv, FaerMatRef T, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_inverse_unit_triangular_upper_in_place_c64(FaerMatMut T_inv, FaerMatRef T, FaerPar par);
+FAER_HIP_API void libfaer_v0_23_inverse_unit_triangular_upper_in_place_c32(FaerMatMut T_inv, FaerMatRef T, FaerPar par);
 
 /* lib.rs:650-655 (cparams! getter)  Auto<T> for LltParams: {64, 128} (cholesky/ldlt/factor.rs:705-714) */
 FAER_HIP_API FaerLltParams libfaer_v0_23_LltParams_f64(void);
@@ -1134,6 +1144,11 @@ FAER_HIP_API void faer_hip_debug_clu_shape(int dtype, size_t out[2]);
 /* tests: the calling thread's last complex partial_piv_lu_factor_in_place -- out = {panels on the LDS leaf, panels on the
  * column-step kernels, column-step launches, interchange launches} */
 FAER_HIP_API void faer_hip_debug_clu_last(size_t out[4]);
+
+/* Complex triangular inverse (ctrtri.hip).
+ * out = {E: edge of the LDS-resident leaf, the number of sub-blocks along that edge -- the leaf inverts E / out[1]-wide diagonal
+ * sub-blocks by substitution and combines them by doubling}; elem_bytes: 8 (c32) or 16 (c64).  Needs no device. */
+FAER_HIP_API void faer_hip_debug_ctrtri_shape(int elem_bytes, size_t out[2]);
 
 #ifdef __cplusplus
 }
